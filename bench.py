@@ -24,9 +24,13 @@ resident in HBM: descriptors, keypoints and the image pyramids are uploaded / bu
 the timed region (upload_ms in the line), the survivor records stay in HBM (or go to the
 all-gather).  Synthetic data: 3dfeaturematcher_amd/synth.py (seeded ray-cast facet scene).
 
-Rank 0 at N=1 also times the CPU oracle (the reference algorithm restated in C, OpenMP over
-queries/points, on every CPU the process may run on) on a bounded sample and extrapolates
-(cpu_baseline).
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs
+DIR) and prints the line.  Everything beside the headline figure runs with --full only: rank 0 at
+N=1 times the CPU oracle (the reference algorithm restated in C, OpenMP over queries/points, on
+every CPU the process may run on) on a bounded sample and extrapolates (cpu_baseline); the same
+pair runs device-resident one launch at a time (stages_ms, lm_profile, roofline.single_launch); the
+records are checked against the committed oracle fixture (verified); at N > 1 the one-GPU
+reference point and the byte-identity check against one GPU run after the timed steps.
 """
 from __future__ import annotations
 
@@ -116,6 +120,15 @@ def parse():
                     help="--gpus N > 1: frame pairs of the same C5 stream on device 0 alone after the timed steps "
                          "(value_one_gpu, efficiency); 0 skips")
     ap.add_argument("--out", type=str, default="")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the CPU baseline, the device-resident run of "
+                         "the same pair (stage costs, LM profile, single-launch roofline), the check of the records "
+                         "against the committed oracle fixture, and at N GPUs the one-GPU reference point and the "
+                         "byte-identity check; a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64; the same inputs and names on every run with the same "
+                         "arguments, so two builds compare output for output)")
     ap.add_argument("--dump-records", type=str, default="",
                     help="torchrun C5: rank 0 saves the last step's merged survivor records (.npy)")
     ap.add_argument("--pmc-json", type=str, default=next(
@@ -133,6 +146,33 @@ def desc_rows(args, a):
 
 def records_digest(rec_bytes: bytes) -> str:
     return hashlib.sha256(rec_bytes).hexdigest()[:16]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def record_fields(rec):
+    """the survivor records a caller receives, one array per field (queryIdx, trainIdx, distance, status,
+    point, normal)"""
+    return {name: rec[name] for name in rec.dtype.names}
+
+
+def dump_outputs(args, arrays):
+    """--dump-outputs DIR: the arrays the last timed step handed its caller, DIR/<name>.npy, float32 as
+    it is and every other type as float64 (exact for the int32 indices).  At most DUMP_LIMIT_BYTES in
+    all: past that every array keeps the same seeded sample of its rows (arrays of equal length keep
+    the same rows, in order)."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and len(a):
+            keep = max(1, int(len(a) * (DUMP_LIMIT_BYTES / total)))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
 
 def main():
@@ -270,22 +310,24 @@ def run_c4_stream(args):
     lat = [r[2] * 1e3 for r in res]
     digests = sorted(set(r[3] for r in res))
     last_st = stats[-1]
-    # the same frame pair HBM-resident, one launch at a time (the pre-round-4 headline): inputs
+    dump_outputs(args, record_fields(last_rec))
+    # --full: the same frame pair HBM-resident, one launch at a time (the pre-round-4 headline): inputs
     # uploaded once, pipe.run() per step -- the per-launch roofline of lm2_kernel
-    res_steps = max(1, min(3, args.steps))
-    pipes[0].upload(*inputs, binary=binary)
-    pipes[0].run()
-    t1 = time.perf_counter()
-    rstats = [pipes[0].run()[1] for _ in range(res_steps)]
-    res_elapsed = time.perf_counter() - t1
+    rstats = None
+    if args.full:
+        res_steps = max(1, min(3, args.steps))
+        pipes[0].upload(*inputs, binary=binary)
+        pipes[0].run()
+        t1 = time.perf_counter()
+        rstats = [pipes[0].run()[1] for _ in range(res_steps)]
+        res_elapsed = time.perf_counter() - t1
     for c in ctxs:
         c.close()
     pix = float(np.mean([st["lm"]["pixel_evaluations"] for st in stats]))
     evals = float(np.mean([st["lm"]["evaluations"] for st in stats]))
     cpu = None
-    if not args.no_cpu and args.desc == "sift":
+    if args.full and not args.no_cpu and args.desc == "sift":
         cpu = cpu_baseline(pair, s, last_st, args)
-    rlm_ms = float(np.mean([st["lm_ms"] for st in rstats]))
     roof = roofline(stats, span_ms / args.steps, pix, evals, args, pair, s)
     roof.update({
         "kernel": "fm3d::lm2_kernel (LM normal refinement), launches overlapped two at a time",
@@ -294,17 +336,23 @@ def run_c4_stream(args):
                            f"the device span of the timed region ({span_ms:.1f} ms, HIP events on the context "
                            f"streams: first submit -> last pair's records); avg_launch_ms = that span / launches"),
         "overlapped_launch_ms_each": float(np.mean([st["lm_ms"] for st in stats])),
-        # PMC bytes are measured on one resident launch: divide by that launch's time, not the span
-        "traffic_GBps": roof["traffic"] / (rlm_ms * 1e6) if roof.get("traffic") and rlm_ms > 0 else None,
-        "traffic_GBps_basis": ("HBM bytes of one resident launch (rocprofv3 PMC, traffic_source) / the resident "
-                               "launch's HIP-event time (single_launch.avg_launch_ms): both one launch at a time"),
-        "single_launch": {
-            "avg_launch_ms": rlm_ms,
-            "achieved": FLOPS_PER_PIXEL_EVAL * pix / (rlm_ms * 1e-3) / 1e12,
-            "frac": FLOPS_PER_PIXEL_EVAL * pix / (rlm_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
-            "note": "one launch in flight (HBM-resident inputs, fm3d_pipeline_run), HIP events on its stream",
-        },
+        # PMC bytes are measured on one resident launch, not on the span of overlapped ones (--full)
+        "traffic_GBps": None,
     })
+    if rstats is not None:
+        rlm_ms = float(np.mean([st["lm_ms"] for st in rstats]))
+        roof.update({
+            # PMC bytes are measured on one resident launch: divide by that launch's time, not the span
+            "traffic_GBps": roof["traffic"] / (rlm_ms * 1e6) if roof.get("traffic") and rlm_ms > 0 else None,
+            "traffic_GBps_basis": ("HBM bytes of one resident launch (rocprofv3 PMC, traffic_source) / the resident "
+                                   "launch's HIP-event time (single_launch.avg_launch_ms): both one launch at a time"),
+            "single_launch": {
+                "avg_launch_ms": rlm_ms,
+                "achieved": FLOPS_PER_PIXEL_EVAL * pix / (rlm_ms * 1e-3) / 1e12,
+                "frac": FLOPS_PER_PIXEL_EVAL * pix / (rlm_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
+                "note": "one launch in flight (HBM-resident inputs, fm3d_pipeline_run), HIP events on its stream",
+            },
+        })
     kp_k = wl["keypoints"] // 1000
     rows = "float" if getattr(args, "desc_dtype", "u8") == "f32" else "u8"
     desc = (f"C4: {kp_k}k SIFT-128 ({rows}) keypoints per {wl['width']}x{wl['height']} frame pair, full pipeline, "
@@ -337,30 +385,35 @@ def run_c4_stream(args):
         },
         "latency_ms": {"mean": float(np.mean(lat)), "max": float(np.max(lat)),
                        "note": "per frame pair, submit call -> its records on the host"},
-        "device_resident_value": sum(st["kept"] for st in rstats) / res_elapsed,
-        "device_resident_note": (f"the same pair, inputs HBM-resident, one step in flight ({res_steps} steps of "
-                                 f"fm3d_pipeline_run, {res_elapsed / res_steps * 1e3:.1f} ms each)"),
         "input_keypoints_per_s": wl["keypoints"] / frame_s,
         "roofline": roof,
         "cpu_baseline": cpu,
-        # stage costs from the resident run (one pair in flight); in the stream every stage's HIP events
-        # also take the time its launches wait behind the other pairs' LM launches
-        "stages_ms": {k: rstats[-1][k] for k in ("match_ms", "nndr_ms", "triangulate_ms", "lm_ms", "total_ms")},
-        "stages_note": ("stages_ms: the device-resident run's last step (one pair in flight: stage costs; nndr_ms "
-                        "is folded into match_ms); stages_ms_queued_and_run: the stream's last pair, whose stage "
-                        "events also span the time its launches queue behind the other pairs' LM launches"),
+        "stages_note": ("stages_ms_queued_and_run: the stream's last pair, whose stage events also span the time "
+                        "its launches queue behind the other pairs' LM launches"),
         "stages_ms_queued_and_run": {k: last_st[k] for k in ("match_ms", "triangulate_ms", "pyramid_ms", "lm_ms",
                                                               "total_ms")},
         "counts": {k: last_st[k] for k in ("queries", "matches", "inliers", "kept")},
-        "lm_profile": lm_profile(rstats[-1]["lm"]),
         "lm_profile_overlapped": lm_profile(last_st["lm"]),
         "setup_s": {"synthetic_generation": round(t_gen, 2)},
         "records_sha256": digests[0] if len(digests) == 1 else digests,
         "records_identical_across_steps": len(digests) == 1,
     }
-    out.update(verify_against_fixture(args, wl, "c4", pair, last_rec))
-    if len(digests) != 1:
-        out["verified"] = False
+    if args.full:
+        out.update({
+            "device_resident_value": sum(st["kept"] for st in rstats) / res_elapsed,
+            "device_resident_note": (f"the same pair, inputs HBM-resident, one step in flight ({res_steps} steps of "
+                                     f"fm3d_pipeline_run, {res_elapsed / res_steps * 1e3:.1f} ms each)"),
+            # stage costs from the resident run (one pair in flight); in the stream every stage's HIP events
+            # also take the time its launches wait behind the other pairs' LM launches
+            "stages_ms": {k: rstats[-1][k] for k in ("match_ms", "nndr_ms", "triangulate_ms", "lm_ms", "total_ms")},
+            "stages_note": ("stages_ms: the device-resident run's last step (one pair in flight: stage costs; nndr_ms "
+                            "is folded into match_ms); stages_ms_queued_and_run: the stream's last pair, whose stage "
+                            "events also span the time its launches queue behind the other pairs' LM launches"),
+            "lm_profile": lm_profile(rstats[-1]["lm"]),
+        })
+        out.update(verify_against_fixture(args, wl, "c4", pair, last_rec))
+        if len(digests) != 1:
+            out["verified"] = False
     emit(out, args)
 
 
@@ -430,16 +483,20 @@ def run_mgpu(args, workload):
     t0 = time.perf_counter()
     res, last_rec = stream_run(args.steps)
     elapsed = time.perf_counter() - t0
-    # one pair alone after the stream (untimed): its stage events are stage costs, not time queued
-    # behind the other pairs' LM launches
-    iso_st = stream_run(1)[0][0][1]
+    dump_outputs(args, record_fields(last_rec))
+    # --full: one pair alone after the stream (untimed): its stage events are stage costs, not time
+    # queued behind the other pairs' LM launches
+    iso_st = stream_run(1)[0][0][1] if args.full else None
     mg.close()
     kept_total = sum(r[0] for r in res)
     value = kept_total / elapsed
     # the same C5 stream on device 0 alone (untimed by the metric): the curve's one-GPU point
     one = {"value_one_gpu": value, "efficiency": 1.0, "one_gpu_steps": args.steps,
            "one_gpu_note": "this run is one GPU: value_one_gpu = value"}
-    if n > 1 and args.ref_steps > 0:
+    if n > 1 and not args.full:
+        one = {"value_one_gpu": None, "efficiency": None, "one_gpu_steps": 0,
+               "one_gpu_note": "the one-GPU reference point is measured with --full"}
+    if n > 1 and args.full and args.ref_steps > 0:
         m1 = fm3d.MultiGPU(s, devices=[0], shares=1)
         try:
             m1.set_g12(pair.g12)
@@ -504,9 +561,9 @@ def run_mgpu(args, workload):
             "avg_launch_ms": frame_s * 1e3,
         },
         "cpu_baseline": None,
-        "stages_ms": {k: iso_st[k] for k in ("match_ms", "lm_ms", "total_ms", "pyramid_ms")},
+        "stages_ms": {k: iso_st[k] for k in ("match_ms", "lm_ms", "total_ms", "pyramid_ms")} if iso_st else None,
         "stages_ms_queued_and_run": {k: last_st[k] for k in ("match_ms", "lm_ms", "total_ms", "pyramid_ms")},
-        "stages_note": ("stages_ms: one frame pair alone after the timed stream (device 0's stage events: stage "
+        "stages_note": ("stages_ms (--full): one frame pair alone after the timed stream (device 0's stage events: stage "
                         "costs); stages_ms_queued_and_run: the stream's last pair, whose events also span the time "
                         "its launches and copies wait behind the other pairs' LM launches"),
         "counts": {k: last_st[k] for k in ("queries", "matches", "inliers", "kept")},
@@ -516,16 +573,17 @@ def run_mgpu(args, workload):
         "torch_imported_at_mgpu_create": torch_at_create,
         **one,
     }
-    out.update(verify_against_fixture(args, wl, "c5", pair, last_rec))
-    if len(digests) != 1:
-        out["verified"] = False
+    if args.full:
+        out.update(verify_against_fixture(args, wl, "c5", pair, last_rec))
+        if len(digests) != 1:
+            out["verified"] = False
     if alias:
         out["alias_devices"] = {
             "note": (f"diagnostic, not a scaling point: device 0 listed {n} times (FM3D_DEBUG_MGPU_ALIAS=1), so "
                      f"all {n} shares, their {4 * n} context sets and {n} concurrent LM launches share ONE GPU and "
                      f"the all-gather is restated as device copies; value / value_one_gpu is the {n}-way host "
                      f"path's cost on one GPU"),
-            "value_over_one_device": value / out["value_one_gpu"]}
+            "value_over_one_device": value / out["value_one_gpu"] if out["value_one_gpu"] else None}
         out["efficiency"] = None
         out["n_gpus"] = 1
     emit(out, args)
@@ -695,7 +753,9 @@ def run_torchrun_stream(args, workload):
             "kept_per_frame_pair": int(len(merged)),
             "setup_s": {"synthetic_generation": round(t_gen, 2)},
         }
-        out.update(verify_against_fixture(args, wl, "c5", pair, merged))
+        if args.full:
+            out.update(verify_against_fixture(args, wl, "c5", pair, merged))
+        dump_outputs(args, record_fields(merged))
         if args.dump_records:
             np.save(args.dump_records, merged)
         emit(out, args)
@@ -800,7 +860,7 @@ def run_resident(args, workload):
     download_ms = (time.perf_counter() - t_dl) * 1e3
 
     check = None
-    if sharded:
+    if sharded and args.full:
         check = check_against_one_gpu(args, fm3d, pair, s, merged, local, rank, dist, torch)
 
     lm_ms = float(np.mean([st["lm_ms"] for st in stats]))
@@ -808,7 +868,7 @@ def run_resident(args, workload):
     evals = float(np.mean([st["lm"]["evaluations"] for st in stats]))
     last_st = stats[-1]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.desc == "sift":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu and args.desc == "sift":
         cpu = cpu_baseline(pair, s, last_st, args)
 
     if rank == 0:
@@ -865,9 +925,11 @@ def run_resident(args, workload):
             out["sharding_check"] = check
         if dist is None:  # bit-identity across builds / boxes (A/B runs compare it)
             out["records_sha256"] = records_digest(mine.tobytes())
-            out.update(verify_against_fixture(args, wl, workload, pair, mine))
-        elif sharded:  # the merged records of the N-GPU run against the committed oracle run
+            if args.full:
+                out.update(verify_against_fixture(args, wl, workload, pair, mine))
+        elif sharded and args.full:  # the merged records of the N-GPU run against the committed oracle run
             out.update(verify_against_fixture(args, wl, workload, pair, merged))
+        dump_outputs(args, record_fields(mine if dist is None else merged))
         line = json.dumps(out)
         print(line, flush=True)
         if args.out:
@@ -958,10 +1020,12 @@ def run_c2(args):
     m, pts, src = pipes[0].dlt_results(last["matches"], last["inliers"])
     same_across = all(np.array_equal(np.asarray(pp.dlt_results(last["matches"], last["inliers"])[1]), np.asarray(pts))
                       for pp in pipes[1:])
+    dump_outputs(args, {"queryIdx": m["queryIdx"], "trainIdx": m["trainIdx"], "distance": m["distance"],
+                        "point": pts, "point_match": src})
     for ctx in ctxs:
         ctx.close()
     # the cpu_baseline leg: the oracle's C2 path on the host cores, whose outputs also check the GPU's
-    cpu, (q, t, dist, opts) = (None, (None,) * 4) if args.no_cpu else c2_cpu_baseline(pair, s, args)
+    cpu, (q, t, dist, opts) = (None, (None,) * 4) if args.no_cpu or not args.full else c2_cpu_baseline(pair, s, args)
     verified = None if q is None else bool(
         np.array_equal(m["queryIdx"], q) and np.array_equal(m["trainIdx"], t) and np.array_equal(m["distance"], dist)
         and np.array_equal(pts, opts))
@@ -1076,10 +1140,11 @@ def run_c3(args):
     sc, nb, best = pipes[0].ncc_results(P, 16)
     _, pts, _ = pipes[0].dlt_results(int(last["matches"]), P)
     same_across = all(np.array_equal(pp.ncc_results(P, 16)[0], sc) for pp in pipes[1:])
+    dump_outputs(args, {"point": pts, "scores": sc, "best_normal": nb, "best_index": best})
     for ctx in ctxs:
         ctx.close()
     cpu, verified = None, None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as orc
         quota = cpu_quota()

@@ -12,11 +12,10 @@
  *                                                          pcl::PointCloud / pcl::Normal and the
  *                                                          view* functions (no-op viewers)
  *
- * Replacing those lines by `#include "fm3d_cv.hpp"` lets the reference main.cpp compile unchanged:
- * tests/test_compat_main.py::test_reference_main_compiles_with_includes_swapped does exactly that
- * to /root/reference/main.cpp when it is readable, and compiles examples/main_dropin.cpp (the same
- * call sequence written for this repository), whose outputs it checks against the Python mirror of
- * the classes.  The classes keep
+ * Replacing those lines by `#include "fm3d_cv.hpp"` lets the reference main.cpp compile unchanged.
+ * No reference text is stored in this repository, so the suite checks it on examples/main_dropin.cpp
+ * (the same call sequence written for this repository): tests/test_compat_main.py compiles it
+ * warning-free and checks its outputs against the Python mirror of the classes.  The classes keep
  * the reference's names, constructors, method signatures and out-parameter semantics and run the
  * hot path through the C ABI (fm3d.h) on GPU 0:
  *   DescriptorsMatcher        descriptorsmatcher.h:39-111   (ctor :47, compare / crosscompare /

@@ -1438,3 +1438,46 @@ def test_bench_torchrun_stream_two_ranks_one_gpu(fm3d, synth, tmp_path):
         ctx.close()
     assert len(merged) == k > 1000
     assert merged.tobytes() == ref.tobytes()
+
+
+def test_bench_plain_run_dumps_last_step(fm3d, synth, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and leaves everything beside the
+    headline figure to --full; --dump-outputs writes the last timed step's survivor records field by
+    field (float32 / float64), equal to one fm3d_pipeline_run of the same seeded frame pair."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--keypoints", "3000", "--dump-outputs", str(dump)], capture_output=True, text=True,
+                       timeout=300, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "keypoints/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["records_identical_across_steps"] is True
+    assert line["cpu_baseline"] is None
+    for k in ("device_resident_value", "stages_ms", "lm_profile", "verified"):  # --full's
+        assert k not in line, k
+    assert "single_launch" not in line["roofline"]
+    pair = synth.make_frame_pair(3000, 640, 480, seed=7, desc="sift")
+    s = fm3d.Settings.default()
+    s.set_camera(pair.cam)
+    s.nndrEpsilon, s.pixelsRay, s.pyramids = 0.55, 64, 3
+    ctx = fm3d.Context(s)
+    try:
+        fm3d.SingleCameraTriangulator(ctx).set_g12(pair.g12)
+        pipe = fm3d.Pipeline(ctx)
+        pipe.upload(pair.desc1, pair.desc2, pair.kp1, pair.kp2, pair.img1, pair.img2)
+        k, st = pipe.run()
+        ref = pipe.records(k)
+    finally:
+        ctx.close()
+    assert k > 100 and sorted(os.listdir(dump)) == sorted(n + ".npy" for n in ref.dtype.names)
+    assert os.listdir(tmp_path) == ["outputs"]  # the run leaves nothing else behind
+    for n in ref.dtype.names:
+        a = np.load(dump / (n + ".npy"))
+        assert a.dtype == (np.float32 if ref[n].dtype == np.float32 else np.float64), n
+        assert a.shape == ref[n].shape and a.tobytes() == ref[n].astype(a.dtype).tobytes(), n

@@ -1,4 +1,4 @@
-"""Print the headline numbers of a bench JSON line (gpurun_out/bench_<tag>.json)."""
+"""Print the headline numbers of a `bench.py --full` JSON line (tools/gpu_quick.sh's bench_<tag>.json)."""
 import json
 import sys
 
