@@ -45,6 +45,7 @@ EXPORTS = (
     "fm3d_mgpu_submit", "fm3d_mgpu_wait", "fm3d_pipeline_link", "fm3d_freak_compute", "fm3d_freak_set_pairs",
     "fm3d_mser_detect", "fm3d_mser_detect_batch", "fm3d_mser_regions", "fm3d_pipeline_submit_dlt", "fm3d_pipeline_submit_dlt_pair",
     "fm3d_pipeline_submit_ncc", "fm3d_pipeline_wait_ncc", "fm3d_pipeline_wait_dlt", "fm3d_device_count",
+    "fm3d_epipolar_matrix", "fm3d_epipolar_lines", "fm3d_knn2_guided", "fm3d_match_nndr_guided",
 )
 
 
@@ -85,6 +86,7 @@ class Settings(ctypes.Structure):
         ("mserMinMargin", ctypes.c_double), ("mserEdgeBlurSize", ctypes.c_int),
         ("lmReduction", ctypes.c_int),
         ("dltSolver", ctypes.c_int),
+        ("guidedMatchPx", ctypes.c_double),
     ]
 
     @staticmethod
@@ -221,6 +223,13 @@ def _desc_type(desc: np.ndarray, binary: bool) -> int:
     raise TypeError("descriptors must be uint8 (SIFT-like), float32 or binary uint8 (binary=True)")
 
 
+def _check_max_px(max_px) -> None:
+    """fm3d_knn2_guided's rule, before any device work: finite and > 0."""
+    v = float(max_px)
+    if not (v > 0.0 and v != float("inf")):
+        raise Fm3dError(ERR_INVALID, "maxPx must be finite and > 0")
+
+
 class DescriptorsMatcher:
     """DescriptorsMatcher (DescriptorsMatcher/descriptorsmatcher.h:39-111), matcher + NNDR part.
 
@@ -281,6 +290,45 @@ class DescriptorsMatcher:
         self.ctx.check(lib().fm3d_match_nndr(self.ctx.handle, _vp(a), a.shape[0], _vp(b), b.shape[0], a.shape[1],
                                              _desc_type(a, self.binary), ctypes.c_double(epsilon), _vp(out),
                                              ctypes.byref(n)))
+        new = out[:n.value].copy()
+        return new if matches is None else np.concatenate([matches, new])
+
+    def knn_match_guided(self, desc_a: np.ndarray, desc_b: np.ndarray, kp1: np.ndarray, kp2: np.ndarray,
+                         max_px: float) -> np.ndarray:
+        """knn_match over the train rows whose keypoint lies within max_px pixels of the query
+        keypoint's epipolar line under the context's g12 (fm3d_knn2_guided) -> (nA, 2) DMATCH array,
+        trainIdx -1 where fewer than two rows pass."""
+        a = np.ascontiguousarray(desc_a)
+        b = np.ascontiguousarray(desc_b)
+        k1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
+        k2 = np.ascontiguousarray(kp2, dtype=np.float32).reshape(-1, 2)
+        if k1.shape[0] != a.shape[0] or k2.shape[0] != b.shape[0]:
+            raise ValueError("one keypoint per descriptor row")
+        _check_max_px(max_px)
+        out = np.zeros((a.shape[0], 2), dtype=DMATCH)
+        self.ctx.check(lib().fm3d_knn2_guided(self.ctx.handle, _vp(a), a.shape[0], _vp(b), b.shape[0], a.shape[1],
+                                              _desc_type(a, self.binary), _vp(k1), _vp(k2), ctypes.c_double(max_px),
+                                              _vp(out)))
+        return out
+
+    def compareWithNNDRGuided(self, epsilon: float, desc_a: np.ndarray, desc_b: np.ndarray, kp1: np.ndarray,
+                              kp2: np.ndarray, max_px: float, matches: np.ndarray | None = None) -> np.ndarray:
+        """compareWithNNDR over the rows that pass knn_match_guided's gate.  A query with a single
+        row on its line is dropped, as the reference's size() >= 2 rule drops it.  New matches are
+        appended to `matches`, as compareWithNNDR appends them."""
+        a = np.ascontiguousarray(desc_a)
+        b = np.ascontiguousarray(desc_b)
+        k1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
+        k2 = np.ascontiguousarray(kp2, dtype=np.float32).reshape(-1, 2)
+        if k1.shape[0] != a.shape[0] or k2.shape[0] != b.shape[0]:
+            raise ValueError("one keypoint per descriptor row")
+        _check_max_px(max_px)
+        out = np.zeros(max(a.shape[0], 1), dtype=DMATCH)
+        n = ctypes.c_int(0)
+        self.ctx.check(lib().fm3d_match_nndr_guided(self.ctx.handle, _vp(a), a.shape[0], _vp(b), b.shape[0],
+                                                    a.shape[1], _desc_type(a, self.binary), _vp(k1), _vp(k2),
+                                                    ctypes.c_double(epsilon), ctypes.c_double(max_px), _vp(out),
+                                                    ctypes.byref(n)))
         new = out[:n.value].copy()
         return new if matches is None else np.concatenate([matches, new])
 
@@ -668,6 +716,15 @@ class SingleCameraTriangulator:
         t2 = np.zeros(3)
         self.ctx.check(lib().fm3d_get_camera2(self.ctx.handle, _ptr(R2), _ptr(t2)))
         return R2.reshape(3, 3), t2
+
+    def epipolar_lines(self, kp1) -> np.ndarray:
+        """fm3d_epipolar_lines: the unit-normal epipolar line (a, b, c, 0) in camera 2's undistorted
+        normalised plane of every image-1 keypoint -> (n, 4) float32; (0, 0, inf, 0) for a
+        degenerate line."""
+        k1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
+        out = np.zeros((k1.shape[0], 4), dtype=np.float32)
+        self.ctx.check(lib().fm3d_epipolar_lines(self.ctx.handle, _vp(k1), k1.shape[0], _vp(out)))
+        return out
 
     def plane_to_image2(self, X, n):
         """fm3d_plane_to_image2 (device kernel): extractPixelsContour(X) and the level-0 projection of
@@ -1126,6 +1183,13 @@ def camera2_from_g12(g12):
     t2 = np.zeros(3)
     _check(lib().fm3d_camera2_from_g12(_ptr(np.ascontiguousarray(g12, dtype=np.float64).ravel()), _ptr(R2), _ptr(t2)))
     return R2.reshape(3, 3), t2
+
+
+def epipolar_matrix(g12) -> np.ndarray:
+    """E = [t2]x R2 of the guided matcher's gate, from camera2_from_g12's (R2, t2) (host only)."""
+    E = np.zeros(9)
+    _check(lib().fm3d_epipolar_matrix(_ptr(np.ascontiguousarray(g12, dtype=np.float64).ravel()), _ptr(E)))
+    return E.reshape(3, 3)
 
 
 class MOSAIC:

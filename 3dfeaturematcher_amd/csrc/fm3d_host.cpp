@@ -110,6 +110,9 @@ struct fm3d_ctx {
     DevBuf partIdx, partKey;  // per-part top-2 lists of the split matchers
     DevBuf A8, B8;            // binary rows unpacked to int8 for the MFMA matcher; u8 rows packed from floats
     DevBuf u8Flag;            // launch_f32_pack_u8's "not integer-valued" flag
+    // the guided matchers' gate (fm3d_kernels.h EpiGate): query lines (float4) and train (u, v)
+    DevBuf gLines, gUV;
+    bool gateStaged = false;  // they belong to the staged pair's keypoints under the current g12
     bool specU8 = false;      // the staged float rows went to the u8 matcher before their flag was read
     // SURF detection / description
     DevBuf sfImg, sfSum, sfDet, sfTr, sfLayers, sfMids, sfCand, sfCount, sfSortTmp, sfFlag, sfPos, sfKp, sfKin, sfSrc,
@@ -303,6 +306,33 @@ void install_g12(fm3d_ctx* c, const double g[16]) {
     std::memcpy(c->g12, g, sizeof(c->g12));
     camera2_from_g12(c->g12, c->R2, c->t2);
     c->haveG12 = true;
+    c->gateStaged = false;  // the staged pair's epipolar lines belong to the previous pose
+}
+
+// E = [t2]x R2, each entry (T[r][0] R2[0][c] + T[r][1] R2[1][c]) + T[r][2] R2[2][c]
+void epipolar_matrix(const double R2[9], const double t2[3], double E[9]) {
+    const double T[9] = {0., -t2[2], t2[1], t2[2], 0., -t2[0], -t2[1], t2[0], 0.};
+    for (int r = 0; r < 3; r++)
+        for (int k = 0; k < 3; k++)
+            E[r * 3 + k] = (T[r * 3 + 0] * R2[0 * 3 + k] + T[r * 3 + 1] * R2[1 * 3 + k]) + T[r * 3 + 2] * R2[2 * 3 + k];
+}
+
+bool good_max_px(double v) { return v > 0. && v <= DBL_MAX; }  // finite and > 0 (false for NaN)
+
+// the gate's device inputs from keypoints already on the device (kp1: nA queries, kp2: nB train
+// rows), queued on the context stream
+int make_gate(fm3d_ctx* c, const fm3d_point2f* kp1, int nA, const fm3d_point2f* kp2, int nB, double maxPx,
+              fm3d::EpiGate* g) {
+    HIPCHK(c, c->gLines.ensure((size_t)nA * sizeof(float4) + 16));
+    HIPCHK(c, c->gUV.ensure((size_t)nB * sizeof(float2) + 16));
+    double E[9];
+    epipolar_matrix(c->R2, c->t2, E);
+    fm3d::launch_epipolar_setup(c->cam, E, kp1, nA, kp2, nB, c->gLines.as<float4>(), c->gUV.as<float2>(), c->stream);
+    HIPCHK(c, hipGetLastError());
+    g->lines = c->gLines.as<float4>();
+    g->uv = c->gUV.as<float2>();
+    g->tau = maxPx * 2.0 / (c->cam.fx + c->cam.fy);
+    return FM3D_OK;
 }
 
 int ensure_offsets(fm3d_ctx* c) {
@@ -515,8 +545,9 @@ int make_lookback(fm3d_ctx* c, int nBlocks, fm3d::LookBack* lb) {
 // compactOut / compactCount (the pipeline): NNDR, the parts' merge (int keys) and the stable
 // compaction of the kept matches in one launch (launch_nndr_compact); else the NNDR flags and
 // candidates in c->flag / c->cand
+// gate (the guided matchers, fm3d_kernels.h EpiGate): every type takes its gated kernels
 int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int queryOffset, bool wantKnn,
-              fm3d_dmatch* compactOut = nullptr, int* compactCount = nullptr) {
+              fm3d_dmatch* compactOut = nullptr, int* compactCount = nullptr, const fm3d::EpiGate* gate = nullptr) {
     const bool fuse = compactOut != nullptr && !wantKnn;
     int mergeParts = 1;  // > 1: the parts' lists are merged by launch_nndr_compact
     HIPCHK(c, c->idx.ensure((size_t)nA * 2 * sizeof(int) + 16));
@@ -545,7 +576,16 @@ int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int
         if (fuse && parts > 1) mergeParts = parts;
         fm3d::launch_knn2_i8(c->A.as<uint8_t>(), nA, c->B.as<uint8_t>(), nB, dimPad, 0, c->cqA.as<int>(),
                              c->ctB.as<int>(), parts, c->partIdx.as<int>(), c->partKey.as<int>(), c->idx.as<int>(),
-                             c->key.as<int>(), c->stream, mergeParts > 1);
+                             c->key.as<int>(), c->stream, mergeParts > 1, gate);
+    } else if (type == FM3D_DESC_F32 && gate) {
+        // no bf16 prefilter here (its bound knows nothing of the gate): the exact scan of the rows inside it
+        const int parts = fm3d::knn2_parts(nA, nB, dimPad, c->nCU);
+        if (parts > 1) {
+            HIPCHK(c, c->partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, c->partKey.ensure((size_t)parts * nA * 2 * sizeof(float) + 16));
+        }
+        fm3d::launch_knn2_f32_gated(c->A.as<float>(), nA, c->B.as<float>(), nB, dimPad, parts, c->partIdx.as<int>(),
+                                    c->partKey.as<float>(), c->idx.as<int>(), c->fkey.as<float>(), *gate, c->stream);
     } else if (type == FM3D_DESC_F32 && (dimPad == 64 || dimPad == 128) && nB >= 64 &&
                (long long)nA * nB >= (1LL << 22) && f32_mfma()) {
         // float rows (SURF): the bf16 MFMA prefilter lists each query's possible top-2 rows, whose exact
@@ -610,7 +650,7 @@ int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int
         if (fuse && parts > 1) mergeParts = parts;
         fm3d::launch_knn2_i8(c->A8.as<uint8_t>(), nA, c->B8.as<uint8_t>(), nB, 256, 1, nullptr, c->ctB.as<int>(),
                              parts, c->partIdx.as<int>(), c->partKey.as<int>(), c->idx.as<int>(), c->key.as<int>(),
-                             c->stream, mergeParts > 1);
+                             c->stream, mergeParts > 1, gate);
     } else {
         const int parts = fm3d::knn2_parts(nA, nB, dimPad, c->nCU);
         if (parts > 1) {
@@ -618,7 +658,7 @@ int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int
             HIPCHK(c, c->partKey.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
         }
         fm3d::launch_knn2_bits(c->A.as<uint8_t>(), nA, c->B.as<uint8_t>(), nB, dimPad, parts, c->partIdx.as<int>(),
-                               c->partKey.as<int>(), c->idx.as<int>(), c->key.as<int>(), c->stream);
+                               c->partKey.as<int>(), c->idx.as<int>(), c->key.as<int>(), c->stream, gate);
     }
     HIPCHK(c, hipGetLastError());
     if (fuse) {
@@ -1731,6 +1771,7 @@ int fm3d_ctx_create(const fm3d_settings* s, int device, fm3d_ctx** out) {
     if (!s || !out) return FM3D_ERR_INVALID;
     *out = nullptr;
     if (s->dltSolver != 0 && s->dltSolver != 1) return FM3D_ERR_INVALID;  // cvSVD or the legacy Jacobi
+    if (!(s->guidedMatchPx >= 0. && s->guidedMatchPx <= DBL_MAX)) return FM3D_ERR_INVALID;  // 0 = off; NaN fails
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return FM3D_ERR_HIP;
     if (device < 0 || device >= n) return FM3D_ERR_INVALID;
@@ -1772,7 +1813,7 @@ void fm3d_ctx_destroy(fm3d_ctx* c) {
                       &c->triPts, &c->triMask, &c->triMask8, &c->pts, &c->srcIdx, &c->lmNormals, &c->lmStatus,
                       &c->lmInfo, &c->lmNfev, &c->lmMdat, &c->lmQueue, &c->lmStat,
                       &c->slab, &c->slabI1,
-                      &c->records, &c->recTmp, &c->recFlag, &c->lmProj, &c->partIdx, &c->partKey, &c->bPairs, &c->f32Work, &c->A8, &c->B8, &c->u8Flag,
+                      &c->records, &c->recTmp, &c->recFlag, &c->lmProj, &c->partIdx, &c->partKey, &c->bPairs, &c->f32Work, &c->A8, &c->B8, &c->u8Flag, &c->gLines, &c->gUV,
                       &c->sfImg, &c->sfSum, &c->sfDet, &c->sfTr, &c->sfLayers, &c->sfMids, &c->sfCand, &c->sfCount,
                       &c->sfSortTmp, &c->sfFlag, &c->sfPos, &c->sfKp, &c->sfKin, &c->sfSrc, &c->sfDesc, &c->sfDW, &c->sfAng,
                       &c->orbPyr, &c->orbTab, &c->orbLev, &c->orbMap, &c->orbFlag, &c->orbPos, &c->orbKp, &c->orbR,
@@ -1840,6 +1881,80 @@ int fm3d_match_nndr(fm3d_ctx* c, const void* descA, int nA, const void* descB, i
     int t, dp, r;
     if ((r = stage_descriptors(c, descA, nA, descB, nB, dim, type, &t, &dp))) return r;
     if ((r = run_match(c, nA, nB, t, dp, epsilon, 0, false))) return r;
+    if ((r = ensure_scan_tmp(c, nA))) return r;
+    HIPCHK(c, c->matches.ensure((size_t)(nA + 1) * sizeof(fm3d_dmatch)));
+    fm3d::launch_compact_dmatch(c->cand.as<fm3d_dmatch>(), c->flag.as<int>(), nA, c->matches.as<fm3d_dmatch>(),
+                                c->count.as<int>(), c->scanTmp.p, c->stream);
+    HIPCHK(c, hipGetLastError());
+    int n = 0;
+    HIPCHK(c, hipMemcpyAsync(&n, c->count.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n) HIPCHK(c, hipMemcpy(matches, c->matches.p, (size_t)n * sizeof(fm3d_dmatch), hipMemcpyDeviceToHost));
+    *nMatches = n;
+    return FM3D_OK;
+}
+
+namespace {
+// descriptors and keypoints of a guided call onto the device, and its gate
+int stage_guided(fm3d_ctx* c, const void* descA, int nA, const void* descB, int nB, int dim, int type,
+                 const fm3d_point2f* kpts1, const fm3d_point2f* kpts2, double maxPx, int* t, int* dp,
+                 fm3d::EpiGate* gate) {
+    if (!c->haveG12) return fail(c, FM3D_ERR_INVALID, "g12 not set (SingleCameraTriangulator::setg12)");
+    if (!good_max_px(maxPx)) return fail(c, FM3D_ERR_INVALID, "maxPx must be finite and > 0");
+    hipSetDevice(c->device);
+    int r;
+    if ((r = stage_descriptors(c, descA, nA, descB, nB, dim, type, t, dp))) return r;
+    if ((r = upload(c, c->kp1, kpts1, (size_t)nA * sizeof(fm3d_point2f)))) return r;
+    if ((r = upload(c, c->kp2, kpts2, (size_t)nB * sizeof(fm3d_point2f)))) return r;
+    c->gateStaged = false;  // (a staged pipeline pair's keypoints are replaced, as fm3d_triangulate replaces them)
+    return make_gate(c, c->kp1.as<fm3d_point2f>(), nA, c->kp2.as<fm3d_point2f>(), nB, maxPx, gate);
+}
+}  // namespace
+
+int fm3d_epipolar_matrix(const double g12[16], double E[9]) {
+    if (!g12 || !E) return FM3D_ERR_INVALID;
+    double R2[9], t2[3];
+    camera2_from_g12(g12, R2, t2);
+    epipolar_matrix(R2, t2, E);
+    return FM3D_OK;
+}
+
+int fm3d_epipolar_lines(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, float* lines) {
+    if (!c || n1 < 0 || (!kpts1 && n1) || (!lines && n1)) return fail(c, FM3D_ERR_INVALID, "null argument");
+    if (!c->haveG12) return fail(c, FM3D_ERR_INVALID, "g12 not set (SingleCameraTriangulator::setg12)");
+    hipSetDevice(c->device);
+    int r;
+    if ((r = upload(c, c->kp1, kpts1, (size_t)n1 * sizeof(fm3d_point2f)))) return r;
+    c->gateStaged = false;
+    fm3d::EpiGate g{};
+    if ((r = make_gate(c, c->kp1.as<fm3d_point2f>(), n1, nullptr, 0, 1.0, &g))) return r;
+    if (n1) HIPCHK(c, hipMemcpyAsync(lines, c->gLines.p, (size_t)n1 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FM3D_OK;
+}
+
+int fm3d_knn2_guided(fm3d_ctx* c, const void* descA, int nA, const void* descB, int nB, int dim, int type,
+                     const fm3d_point2f* kpts1, const fm3d_point2f* kpts2, double maxPx, fm3d_dmatch* out) {
+    if (!c || (!descA && nA) || (!descB && nB) || (!out && nA) || (!kpts1 && nA) || (!kpts2 && nB))
+        return fail(c, FM3D_ERR_INVALID, "null argument");
+    int t, dp, r;
+    fm3d::EpiGate gate{};
+    if ((r = stage_guided(c, descA, nA, descB, nB, dim, type, kpts1, kpts2, maxPx, &t, &dp, &gate))) return r;
+    if ((r = run_match(c, nA, nB, t, dp, 0.0, 0, true, nullptr, nullptr, &gate))) return r;
+    if (nA) HIPCHK(c, hipMemcpyAsync(out, c->knnOut.p, (size_t)nA * 2 * sizeof(fm3d_dmatch), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FM3D_OK;
+}
+
+int fm3d_match_nndr_guided(fm3d_ctx* c, const void* descA, int nA, const void* descB, int nB, int dim, int type,
+                           const fm3d_point2f* kpts1, const fm3d_point2f* kpts2, double epsilon, double maxPx,
+                           fm3d_dmatch* matches, int* nMatches) {
+    if (!c || !nMatches || (!descA && nA) || (!descB && nB) || (!matches && nA) || (!kpts1 && nA) || (!kpts2 && nB))
+        return fail(c, FM3D_ERR_INVALID, "null argument");
+    int t, dp, r;
+    fm3d::EpiGate gate{};
+    if ((r = stage_guided(c, descA, nA, descB, nB, dim, type, kpts1, kpts2, maxPx, &t, &dp, &gate))) return r;
+    if ((r = run_match(c, nA, nB, t, dp, epsilon, 0, false, nullptr, nullptr, &gate))) return r;
     if ((r = ensure_scan_tmp(c, nA))) return r;
     HIPCHK(c, c->matches.ensure((size_t)(nA + 1) * sizeof(fm3d_dmatch)));
     fm3d::launch_compact_dmatch(c->cand.as<fm3d_dmatch>(), c->flag.as<int>(), nA, c->matches.as<fm3d_dmatch>(),
@@ -2058,6 +2173,7 @@ int stage_pipeline(fm3d_ctx* c, const void* descA, int nA, const void* descB, in
     c->stDimPad = dp;
     c->stQueryOffset = queryOffset;
     c->staged = true;
+    c->gateStaged = false;
     return FM3D_OK;
 }
 
@@ -2071,12 +2187,26 @@ int pipeline_front(fm3d_ctx* c) {
     hipEvent_t* ev = c->ev;
     HIPCHK(c, c->pcnt.ensure(64));
     int* cnt = c->pcnt.as<int>();
+    // Fm3d.guidedMatchPx: the epipolar gate over the staged keypoints (kp1 holds this share's queries),
+    // its lines and (u, v) computed once per upload and pose
+    fm3d::EpiGate gate{};
+    const bool guided = c->s.guidedMatchPx > 0.;
+    if (guided) {
+        if (!c->gateStaged) {
+            if ((r = make_gate(c, c->kp1.as<fm3d_point2f>(), nA, c->kp2.as<fm3d_point2f>(), nB, c->s.guidedMatchPx, &gate)))
+                return r;
+            c->gateStaged = true;
+        }
+        gate.lines = c->gLines.as<float4>();
+        gate.uv = c->gUV.as<float2>();
+        gate.tau = c->s.guidedMatchPx * 2.0 / (c->cam.fx + c->cam.fy);
+    }
     HIPCHK(c, hipEventRecord(ev[2], c->stream));
     // a1: match + NNDR (+ the stable compaction of the kept matches, fused into the NNDR launch)
     if ((r = ensure_scan_tmp(c, nA))) return r;
     HIPCHK(c, c->matches.ensure((size_t)(nA + 1) * sizeof(fm3d_dmatch)));
     if ((r = run_match(c, nA, nB, c->stType, c->stDimPad, c->s.nndrEpsilon, c->stQueryOffset, false,
-                       c->matches.as<fm3d_dmatch>(), cnt + 0)))
+                       c->matches.as<fm3d_dmatch>(), cnt + 0, guided ? &gate : nullptr)))
         return r;
     // the stage boundaries (ev[3]: match + NNDR done, ev[5]: DLT done) only when asked for: a timed
     // event between two launches costs the C2 step 4-10 us of gap (rocprofv3 trace, round 5);
@@ -2396,6 +2526,7 @@ int fm3d_internal_memory_need(fm3d_ctx* c, int64_t nA, int64_t nB, int dim, int 
     const size_t rowIn = type == FM3D_DESC_F32 ? (size_t)dim * 4 : (size_t)dim;
     const size_t rowWork = 256 + (type == FM3D_DESC_F32 ? (size_t)dim * 4 : 0);  // u8 / unpacked / pair copies
     need += (size_t)(nA + nB) * (rowIn + rowWork) + (size_t)nB * 64;
+    if (c->s.guidedMatchPx > 0.) need += (size_t)nA * 16 + (size_t)nB * 8;  // the gate's lines and (u, v)
     need += (size_t)nA * 1536;  // per query: top-2 lists + 16 parts, matches, points, masks, LM arrays, records
     need += (size_t)width * height * 4 + ((size_t)16 << 20);  // pyramids with guards, small buffers
     *bytes = need;

@@ -111,6 +111,20 @@ struct KnnOut {
     float* fkey;    // nA x 2 (f32: FLANN squared distance)
 };
 
+// The epipolar gate of the guided matchers: query i ranks train row j only when
+//   |((double)a_i * u_j + (double)b_i * v_j) + (double)c_i| <= tau
+// with (a, b, c, 0) = lines[i] (launch_epipolar_setup; (0, 0, +inf, 0) passes no row) and
+// (u, v) = uv[j].  A null gate pointer at a launcher selects the ungated kernels.
+struct EpiGate {
+    const float4* lines;  // nA query lines
+    const float2* uv;     // nB undistorted train keypoints
+    double tau;           // maxPx * 2 / (fx + fy)
+};
+// lines[i] of kp1[i] (n1 queries) under E (row-major 3 x 3) and uv[j] = undistort1(kp2[j]) (n2 train
+// rows), both rounded to float, in one launch
+void launch_epipolar_setup(const Camera& cam, const double E[9], const fm3d_point2f* kp1, int n1,
+                           const fm3d_point2f* kp2, int n2, float4* lines, float2* uv, hipStream_t s);
+
 // u8 rows (dim padded to a multiple of 128 with value 128 on both sides -> no effect)
 // u8 rows: `parts` train-tile ranges (knn2_u8_parts), merged through partIdx/partKey
 int knn2_u8_parts(int nA, int nB, int nCU, int qPerBlock, int tileRows);
@@ -121,7 +135,7 @@ int knn2_i8_tile_rows(int dimPad, int bits);
 // deferMerge: with parts > 1 the parts' lists stay in partIdx / partKey (launch_nndr_compact merges them)
 void launch_knn2_i8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimPad, int bits, const int* cqA,
                     const int* ctB, int parts, int* partIdx, int* partKey, int* idx, int* key, hipStream_t s,
-                    bool deferMerge = false);
+                    bool deferMerge = false, const EpiGate* gate = nullptr);
 // row constants of both sides: cq = |a'|^2 per query row, ctp = packed train constants
 void launch_rowconst_u8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimPad, int* cq, int* ctp,
                         hipStream_t s);
@@ -137,6 +151,10 @@ int knn2_parts(int nA, int nB, int dim, int nCU);
 size_t knn2_f32_pairs_bytes(int nB, int dim);  // the row-pair copy of B (dim 64 / 128)
 void launch_knn2_f32(const float* A, int nA, const float* B, int nB, int dim, int parts, int* partIdx,
                      float* partKey, float* pairs, int* idx, float* key, hipStream_t s);
+// f32 rows of any dim over the rows that pass the gate: the generic scan's scheme (FLANN order,
+// strictly smaller replaces) over `parts` train ranges, merged as launch_knn2_f32 merges them
+void launch_knn2_f32_gated(const float* A, int nA, const float* B, int nB, int dim, int parts, int* partIdx,
+                           float* partKey, int* idx, float* key, const EpiGate& gate, hipStream_t s);
 // f32 rows (dim 64 / 128) through the bf16 MFMA prefilter (fm3d_match.hip): the same top-2 and keys
 // as launch_knn2_f32; work: knn2_f32_mfma_bytes(nA, nB, dim, parts) bytes of device scratch
 size_t knn2_f32_mfma_bytes(int nA, int nB, int dim, int parts);
@@ -151,7 +169,7 @@ void launch_knn2_f32_mfma_rescan(const float* A, const float* B, int nB, int dim
                                  int nResc, int* idx, float* key, hipStream_t s);
 // binary rows: `parts` train ranges (knn2_parts), merged through partIdx/partKey
 void launch_knn2_bits(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimBytes, int parts, int* partIdx,
-                      int* partKey, int* idx, int* key, hipStream_t s);
+                      int* partKey, int* idx, int* key, hipStream_t s, const EpiGate* gate = nullptr);
 // distances + NNDR flag per query; type 0 f32 keys in fkey, 1 u8, 2 bits
 void launch_nndr(int type, const int* idx, const int* key, const float* fkey, int nA, int nB, double eps,
                  int queryOffset, fm3d_dmatch* knnOut, fm3d_dmatch* cand, int* flag, hipStream_t s);

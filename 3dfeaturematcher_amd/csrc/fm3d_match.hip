@@ -163,12 +163,23 @@ __global__ void unpack_bits_kernel(const uint32_t* __restrict__ A, int nA, const
 // popc(b) - a.b', no query constant).  QG: 32-query groups per wave (a workgroup holds kQ * QG
 // queries); each A fragment read from LDS feeds QG MFMAs, and the per-tile staging, barrier and
 // merge are shared by QG groups.
-template <int KS, bool BITS, int QG, int TR = kT>
+// GATE: the guided matcher (fm3d_kernels.h EpiGate).  A lane's queries' lines stay in registers,
+// the tile's (u, v) are staged in LDS next to ctl, and the epilogue zeroes the packed key ("no row")
+// of a pair outside the gate; ranking, merges and outputs are the ungated kernel's.
+template <bool GATE>
+struct GateArgs {};
+template <>
+struct GateArgs<true> {
+    const float4* lines;
+    const float2* uv;
+    double tau;
+};
+template <int KS, bool BITS, int QG, int TR = kT, bool GATE = false>
 __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __restrict__ A, int nA,
                                                            const uint8_t* __restrict__ B, int nB, int dimPad,
                                                            const int* __restrict__ cqA, const int* __restrict__ ctB,
                                                            int tilesPerPart, int* __restrict__ idxOut,
-                                                           int* __restrict__ keyOut) {
+                                                           int* __restrict__ keyOut, GateArgs<GATE> gate) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert(TR == 128 || (TR == 256 && KS == 4 && !BITS), "256-row tiles: 128-byte u8 rows only");
     constexpr int kRB = TR == 256 ? 8 : 7;                 // row bits of a packed key
@@ -177,6 +188,7 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
     const int tileBytes = TR * (KS ? 32 * KS : dimPad);
     unsigned char* tiles = smem;                              // 2 x tileBytes
     uint32_t* ctl = (uint32_t*)(smem + 2 * (size_t)tileBytes);  // 2 x TR packed row constants
+    float2* uvl = (float2*)(ctl + 2 * TR);                      // GATE: 2 x TR train (u, v)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q0 = blockIdx.x * (kQ * QG) + wave * 32 * QG;
     const int half = lane >> 5;
@@ -206,6 +218,20 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
         b1[g] = b2[g] = INT_MAX;
         i1[g] = i2[g] = -1;
     }
+    // GATE: this lane's query lines; a lane without a query passes no row
+    double la[QG], lb[QG], lc[QG], tau = 0.;
+    if constexpr (GATE) {
+        tau = gate.tau;
+#pragma unroll
+        for (int g = 0; g < QG; g++) {
+            const int qrow = q0 + 32 * g + (lane & 31);
+            float4 l = make_float4(0.f, 0.f, __builtin_inff(), 0.f);
+            if (qrow < nA) l = gate.lines[qrow];
+            la[g] = (double)l.x;
+            lb[g] = (double)l.y;
+            lc[g] = (double)l.z;
+        }
+    }
     // train tiles of this part (blockIdx.y): [tBeg, tEnd); the parts' lists are merged by knn2_int_merge
     const int tBeg = blockIdx.y * tilesPerPart;
     const int tEnd = min((nB + TR - 1) / TR, tBeg + tilesPerPart);
@@ -216,6 +242,7 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
     const int total = TR * chunksPerRow;
     v4i pre[kPre];
     uint32_t preCt = 0;
+    float2 preUV = make_float2(0.f, 0.f);
     auto load_tile = [&](int t) {
         // rows past nB only in the last tile: the others load without a per-chunk test
         const uint8_t* tb = B + (size_t)t * TR * rowBytes;
@@ -237,6 +264,7 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
         if (tid < TR) {
             const int j = t * TR + tid;
             preCt = (j < nB) ? (uint32_t)ctB[j] : 0u;
+            if constexpr (GATE) preUV = (j < nB) ? gate.uv[j] : make_float2(0.f, 0.f);
         }
     };
     auto store_tile = [&](int buf) {
@@ -250,7 +278,10 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
                     pre[i] ^ (v4i){kFlip, kFlip, kFlip, kFlip};
             }
         }
-        if (tid < TR) ctl[buf * TR + tid] = preCt;
+        if (tid < TR) {
+            ctl[buf * TR + tid] = preCt;
+            if constexpr (GATE) uvl[buf * TR + tid] = preUV;
+        }
     };
     struct Acc {
         v16i a[QG];
@@ -266,6 +297,7 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
         if (t + 1 < tEnd) load_tile(t + 1);
         const unsigned char* tl = tiles + (size_t)buf * tileBytes;
         const uint32_t* ct = ctl + buf * TR;
+        const float2* uvt = uvl + buf * TR;
         // packed top-2 (largest) of this tile per query group, two chains (even / odd row blocks)
         // merged after the tile
         uint32_t p1[QG][2], p2[QG][2];
@@ -294,6 +326,28 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
             // tested against one per-lane limit (the row offsets stay compile-time constants)
             const int c = rb & 1;
             const int lim = nB - t * TR - 4 * half;
+            if constexpr (GATE) {
+                // row-major here: a row's (u, v) are read and widened once for the QG groups
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const float2 w = uvt[row];
+                    const double u = (double)w.x, vv = (double)w.y;
+                    const uint32_t ctr = ct[row];
+#pragma unroll
+                    for (int g = 0; g < QG; g++) {
+                        uint32_t v = ((uint32_t)acc.a[g][r] << kShift) + ctr;
+                        // products of two floats are exact in double: the fused form has the unfused bits
+                        const double d = __builtin_fabs(__builtin_fma(la[g], u, lb[g] * vv) + lc[g]);
+                        bool in = d <= tau;  // false for NaN
+                        if (!decltype(fullc)::value) in = in && (rb * 32 + (r & 3) + 8 * (r >> 2) < lim);
+                        v = in ? v : 0u;
+                        p2[g][c] = med3u(p1[g][c], p2[g][c], v);
+                        p1[g][c] = umax(p1[g][c], v);
+                    }
+                }
+                return;
+            }
 #pragma unroll
             for (int g = 0; g < QG; g++) {
 #pragma unroll
@@ -1082,6 +1136,73 @@ __global__ __launch_bounds__(256) void knn2_f32_rescan_kernel(const float* __res
     }
 }
 
+// ---------------- guided matching: the exact scans over the rows inside the gate ----------------
+// (fm3d_kernels.h EpiGate; the int8-MFMA kernel has its own GATE form.)  One query per thread, its
+// line in registers; a train row outside the gate costs its (u, v) load and five fp64 operations,
+// a row inside it the full distance.  blockIdx.y selects a train range, merged as the ungated parts.
+__device__ inline bool gate_pass(double a, double b, double c, float2 w, double tau) {
+    // products of two floats are exact in double: the fused form has the unfused form's bits
+    return __builtin_fabs(__builtin_fma(a, (double)w.x, b * (double)w.y) + c) <= tau;  // false for NaN
+}
+
+// knn2_f32_generic_kernel's scheme (FLANN's groups of four, strictly smaller replaces), any dim
+__global__ __launch_bounds__(256) void knn2_f32_gated_kernel(const float* __restrict__ A, int nA,
+                                                             const float* __restrict__ B, int nB, int dim,
+                                                             int rowsPerPart, const float4* __restrict__ lines,
+                                                             const float2* __restrict__ uv, double tau,
+                                                             int* __restrict__ idxOut, float* __restrict__ keyOut) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nA) return;
+    const int jBeg = blockIdx.y * rowsPerPart;
+    const int jEnd = min(nB, jBeg + rowsPerPart);
+    const float4 l = lines[q];
+    const double la = (double)l.x, lb = (double)l.y, lc = (double)l.z;
+    const float* a = A + (size_t)q * dim;
+    float b1 = __builtin_inff(), b2 = __builtin_inff();
+    int i1 = -1, i2 = -1;
+    for (int j = jBeg; j < jEnd; j++) {
+        if (!gate_pass(la, lb, lc, uv[j], tau)) continue;
+        top2_insert_f(flann_l2(a, B + (size_t)j * dim, dim), j, b1, i1, b2, i2);
+    }
+    const size_t o = ((size_t)blockIdx.y * nA + q) * 2;
+    idxOut[o] = i1;
+    idxOut[o + 1] = i2;
+    keyOut[o] = b1;
+    keyOut[o + 1] = b2;
+}
+
+// the popcount scan (binary rows that do not take the MFMA kernel: 16 and 64 bytes)
+template <int NW>
+__global__ __launch_bounds__(256) void knn2_bits_gated_kernel(const uint32_t* __restrict__ A, int nA,
+                                                              const uint32_t* __restrict__ B, int nB,
+                                                              int rowsPerPart, const float4* __restrict__ lines,
+                                                              const float2* __restrict__ uv, double tau,
+                                                              int* __restrict__ idxOut, int* __restrict__ keyOut) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nA) return;
+    const int jBeg = blockIdx.y * rowsPerPart;
+    const int jEnd = min(nB, jBeg + rowsPerPart);
+    const float4 l = lines[q];
+    const double la = (double)l.x, lb = (double)l.y, lc = (double)l.z;
+    uint32_t a[NW];
+#pragma unroll
+    for (int w = 0; w < NW; w++) a[w] = A[(size_t)q * NW + w];
+    int b1 = INT_MAX, b2 = INT_MAX, i1 = -1, i2 = -1;
+    for (int j = jBeg; j < jEnd; j++) {
+        if (!gate_pass(la, lb, lc, uv[j], tau)) continue;
+        const uint32_t* r = B + (size_t)j * NW;
+        int h = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) h += __popc(a[w] ^ r[w]);
+        top2_insert(h, j, b1, i1, b2, i2);
+    }
+    const size_t o = ((size_t)blockIdx.y * nA + q) * 2;
+    idxOut[o] = i1;
+    idxOut[o + 1] = i2;
+    keyOut[o] = b1;
+    keyOut[o + 1] = b2;
+}
+
 // Float rows handed over as the reference's cv::Mat of SIFT descriptors (descriptorsmatcher.cpp:114-117)
 // that hold integers in [0, 255] (OpenCV's SIFT saturates to uchar before the float conversion): each
 // thread packs 4 bytes of a u8 row padded to dimPad (pad value 128) for the int8-MFMA kernel, both
@@ -1150,10 +1271,10 @@ void launch_unpack_bits(const uint8_t* A, int nA, const uint8_t* B, int nB, uint
 
 void launch_knn2_i8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimPad, int bits, const int* cqA,
                     const int* ctB, int parts, int* partIdx, int* partKey, int* idx, int* key, hipStream_t s,
-                    bool deferMerge) {
+                    bool deferMerge, const EpiGate* gate) {
     if (nA <= 0) return;
     const int TRv = knn2_i8_tile_rows(dimPad, bits);
-    size_t lds = 2 * (size_t)TRv * dimPad + 2 * TRv * sizeof(int);
+    size_t lds = 2 * (size_t)TRv * dimPad + 2 * TRv * sizeof(int) + (gate ? 2 * TRv * sizeof(float2) : 0);
     const int nTiles = (nB + TRv - 1) / TRv;
     const int tilesPerPart = parts > 1 ? (nTiles + parts - 1) / parts : (nTiles > 0 ? nTiles : 1);
     int* oi = parts > 1 ? partIdx : idx;
@@ -1162,9 +1283,27 @@ void launch_knn2_i8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimP
         if (lds > 65536)
             (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         const dim3 g((nA + kQ * qg - 1) / (kQ * qg), parts);
-        kernel<<<g, kThreads, lds, s>>>(A, nA, B, nB, dimPad, cqA, ctB, tilesPerPart, oi, ok);
+        kernel<<<g, kThreads, lds, s>>>(A, nA, B, nB, dimPad, cqA, ctB, tilesPerPart, oi, ok, GateArgs<false>{});
     };
-    if (bits)
+    auto goGated = [&](auto kernel, int qg) {
+        if (lds > 65536)
+            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const dim3 g((nA + kQ * qg - 1) / (kQ * qg), parts);
+        kernel<<<g, kThreads, lds, s>>>(A, nA, B, nB, dimPad, cqA, ctB, tilesPerPart, oi, ok,
+                                        GateArgs<true>{gate->lines, gate->uv, gate->tau});
+    };
+    if (gate) {
+        // the same tile rows and queries per block as the ungated forms (knn2_i8_tile_rows,
+        // knn2_i8_queries_per_block: the row constants' packing and the part count depend on them)
+        if (bits)
+            goGated(knn2_i8_kernel<8, true, 1, kT, true>, 1);
+        else if (dimPad == 128)
+            goGated(knn2_i8_kernel<4, false, kQG128, kTR128, true>, kQG128);
+        else if (dimPad == 256)
+            goGated(knn2_i8_kernel<8, false, 1, kT, true>, 1);
+        else
+            goGated(knn2_i8_kernel<0, false, 1, kT, true>, 1);
+    } else if (bits)
         go(knn2_i8_kernel<8, true, 1>, 1);  // 32-byte binary rows unpacked to 256 int8
     else if (dimPad == 128)
         go(knn2_i8_kernel<4, false, kQG128, kTR128>, kQG128);
@@ -1360,8 +1499,19 @@ void launch_knn2_f32(const float* A, int nA, const float* B, int nB, int dim, in
     if (parts > 1) knn2_f32_merge<<<grid, 256, 0, s>>>(partIdx, partKey, nA, parts, idx, key);
 }
 
+void launch_knn2_f32_gated(const float* A, int nA, const float* B, int nB, int dim, int parts, int* partIdx,
+                           float* partKey, int* idx, float* key, const EpiGate& gate, hipStream_t s) {
+    if (nA <= 0) return;
+    const int grid = (nA + 255) / 256;
+    const int rowsPerPart = parts > 1 ? (nB + parts - 1) / parts : (nB > 0 ? nB : 1);
+    const dim3 g(grid, parts);
+    knn2_f32_gated_kernel<<<g, 256, 0, s>>>(A, nA, B, nB, dim, rowsPerPart, gate.lines, gate.uv, gate.tau,
+                                            parts > 1 ? partIdx : idx, parts > 1 ? partKey : key);
+    if (parts > 1) knn2_f32_merge<<<grid, 256, 0, s>>>(partIdx, partKey, nA, parts, idx, key);
+}
+
 void launch_knn2_bits(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimBytes, int parts, int* partIdx,
-                      int* partKey, int* idx, int* key, hipStream_t s) {
+                      int* partKey, int* idx, int* key, hipStream_t s, const EpiGate* gate) {
     if (nA <= 0) return;
     const int grid = (nA + 255) / 256;
     const uint32_t* a = (const uint32_t*)A;
@@ -1370,6 +1520,18 @@ void launch_knn2_bits(const uint8_t* A, int nA, const uint8_t* B, int nB, int di
     const dim3 g(grid, parts);
     int* oi = parts > 1 ? partIdx : idx;
     int* ok = parts > 1 ? partKey : key;
+    if (gate) {
+        const float4* gl = gate->lines;
+        const float2* gu = gate->uv;
+        const double tau = gate->tau;
+        switch (dimBytes / 4) {
+            case 8: knn2_bits_gated_kernel<8><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
+            case 4: knn2_bits_gated_kernel<4><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
+            default: knn2_bits_gated_kernel<16><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
+        }
+        if (parts > 1) knn2_int_merge<<<grid, 256, 0, s>>>(partIdx, partKey, nA, parts, idx, key);
+        return;
+    }
     switch (dimBytes / 4) {
         case 8: knn2_bits_sgpr_kernel<8><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, oi, ok); break;
         case 4: knn2_bits_sgpr_kernel<4><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, oi, ok); break;

@@ -200,6 +200,36 @@ __global__ void undistort_kernel(Camera cam, const double* __restrict__ xy, int 
     undistort1(cam, xy[2 * i], xy[2 * i + 1], out[2 * i], out[2 * i + 1]);
 }
 
+// The guided matchers' inputs, one thread per keypoint, both frames in one launch.
+// Thread i < n1: the epipolar line l = E (x, y, 1) of query keypoint i in camera 2's undistorted
+// normalised plane, scaled to a unit normal and rounded to float: lines[i] = (a, b, c, 0); a line
+// without a normal (n == 0) or with a non-finite coefficient becomes (0, 0, +inf, 0), which no point
+// passes.  Thread n1 + j: uv[j] = undistort1(kp2[j]) rounded to float.
+struct EpiMat {
+    double e[9];
+};
+__global__ void epipolar_lines_kernel(Camera cam, EpiMat E, const fm3d_point2f* __restrict__ kp1, int n1,
+                                      const fm3d_point2f* __restrict__ kp2, int n2, float4* __restrict__ lines,
+                                      float2* __restrict__ uv) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n1 + n2) return;
+    const fm3d_point2f k = i < n1 ? kp1[i] : kp2[i - n1];
+    double x, y;
+    undistort1(cam, (double)k.x, (double)k.y, x, y);
+    if (i >= n1) {
+        uv[i - n1] = make_float2((float)x, (float)y);
+        return;
+    }
+    const double l0 = (E.e[0] * x + E.e[1] * y) + E.e[2];
+    const double l1 = (E.e[3] * x + E.e[4] * y) + E.e[5];
+    const double l2 = (E.e[6] * x + E.e[7] * y) + E.e[8];
+    const double n = sqrt(l0 * l0 + l1 * l1);
+    const float a = (float)(l0 / n), b = (float)(l1 / n), c = (float)(l2 / n);
+    const float inf = __builtin_inff();
+    const bool ok = n != 0. && fabsf(a) < inf && fabsf(b) < inf && fabsf(c) < inf;  // NaN compares false
+    lines[i] = ok ? make_float4(a, b, c, 0.f) : make_float4(0.f, 0.f, inf, 0.f);
+}
+
 // extractPixelsContour(X) (singlecameratriangulator.cpp:341-397) and, for every kept pixel,
 // get3dPointsFromImage1Pixels (:530-574: undistortPoints, projectPointToPlane :421-470,
 // isInBoundingBox :646-655) + projectPointsToImage2 (:591-626) at scale 1 through the plane (X, n):
@@ -487,6 +517,14 @@ void launch_plane_project(const PlaneProjParams& p, hipStream_t s) {
 void launch_undistort(const Camera& cam, const double* xy, int n, double* out, hipStream_t s) {
     if (n <= 0) return;
     undistort_kernel<<<(n + 255) / 256, 256, 0, s>>>(cam, xy, n, out);
+}
+
+void launch_epipolar_setup(const Camera& cam, const double E[9], const fm3d_point2f* kp1, int n1,
+                           const fm3d_point2f* kp2, int n2, float4* lines, float2* uv, hipStream_t s) {
+    if (n1 + n2 <= 0) return;
+    EpiMat m;
+    for (int k = 0; k < 9; k++) m.e[k] = E[k];
+    epipolar_lines_kernel<<<(n1 + n2 + 255) / 256, 256, 0, s>>>(cam, m, kp1, n1, kp2, n2, lines, uv);
 }
 
 size_t scan_tmp_bytes(int n) { return sizeof(int) * ((size_t)(n + kScanBlock - 1) / kScanBlock + 16); }

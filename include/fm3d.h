@@ -126,6 +126,12 @@ typedef struct fm3d_settings {
        the default, the parity contract; 1 = the 4-row system and a round-robin Jacobi of rounds 1-5
        (opt-in; its points leave OpenCV's in the last bits) */
     int dltSolver;
+    /* Epipolar-guided matching (not a reference key; Fm3d.guidedMatchPx in the settings file): when > 0
+       the pipeline's match stage ranks, for every query, only the train keypoints within this many
+       pixels of the query's epipolar line under g12 (fm3d_knn2_guided's gate);
+       0 = off, the default and the parity contract.  fm3d_ctx_create rejects negative and
+       non-finite values. */
+    double guidedMatchPx;
 } fm3d_settings;
 
 #define FM3D_FEAT_SURF 0
@@ -237,6 +243,19 @@ int fm3d_knn2(fm3d_ctx *ctx, const void *descA, int nA, const void *descB, int n
    matches: capacity nA, written in query order; *nMatches = count. */
 int fm3d_match_nndr(fm3d_ctx *ctx, const void *descA, int nA, const void *descB, int nB, int dim, int type,
                     double epsilon, fm3d_dmatch *matches, int *nMatches);
+/* Epipolar-guided forms of the two above (no reference counterpart: the reference knows g12 before it
+   matches, main.cpp:96-114, and ignores it).  kpts1 / kpts2: one keypoint per row of descA / descB.
+   Query i ranks only the train rows j with |a u + b v + c| <= maxPx * 2 / (Fx + Fy), (a, b, c) =
+   fm3d_epipolar_lines' line of kpts1[i] and (u, v) = the undistorted kpts2[j] rounded to float, the sum
+   in double.  Order, ties and distances as fm3d_knn2; a query with fewer than two
+   rows inside the gate gets the missing entries fm3d_knn2 gives when nB < 2, and the NNDR rule then
+   drops it (a single candidate on the line is dropped, as the reference's size() >= 2 drops it).
+   FM3D_ERR_INVALID: a null pointer, g12 not set, maxPx not finite or not > 0. */
+int fm3d_knn2_guided(fm3d_ctx *ctx, const void *descA, int nA, const void *descB, int nB, int dim, int type,
+                     const fm3d_point2f *kpts1, const fm3d_point2f *kpts2, double maxPx, fm3d_dmatch *out);
+int fm3d_match_nndr_guided(fm3d_ctx *ctx, const void *descA, int nA, const void *descB, int nB, int dim, int type,
+                           const fm3d_point2f *kpts1, const fm3d_point2f *kpts2, double epsilon, double maxPx,
+                           fm3d_dmatch *matches, int *nMatches);
 
 /* ---------------- SingleCameraTriangulator ---------------- */
 /* setg12 (singlecameratriangulator.cpp:123-143): g12 = gIC^-1 g2^-1 g1 gIC, row-major 4x4 */
@@ -250,6 +269,15 @@ int fm3d_camera2_from_g12(const double g12[16], double R2[9], double t2[3]);
 int fm3d_set_g12(fm3d_ctx *ctx, const double g12[16]);
 /* R2, t2 that projectPointsToImage2 projects with: Rodrigues(Rodrigues^-1(R12)), t12 (:591-602) */
 int fm3d_get_camera2(const fm3d_ctx *ctx, double R2[9], double t2[3]);
+/* E = [t2]x R2 (row-major 3 x 3) from the (R2, t2) of fm3d_camera2_from_g12: x2^T E x1 = 0 for the
+   undistorted normalised coordinates of one scene point in both views.  Pure host algebra, usable
+   without a GPU; E[r][c] = (T[r][0] R2[0][c] + T[r][1] R2[1][c]) + T[r][2] R2[2][c]. */
+int fm3d_epipolar_matrix(const double g12[16], double E[9]);
+/* The epipolar line in camera 2 of every image-1 keypoint: l = E (x, y, 1) with (x, y) the keypoint
+   through undistortPoints, scaled to a unit normal and rounded to float.  lines: n1 x 4 floats
+   (a, b, c, 0); a degenerate line (no normal, or a non-finite coefficient) is (0, 0, +inf, 0), which
+   no point passes.  FM3D_ERR_INVALID when g12 is not set. */
+int fm3d_epipolar_lines(fm3d_ctx *ctx, const fm3d_point2f *kpts1, int n1, float *lines);
 /* setKeypoints (:145-171) + triangulate (:173-230).  points: capacity 3*nMatches (compacted,
    match order); inlierMask: nMatches bytes (the outliersMask). */
 int fm3d_triangulate(fm3d_ctx *ctx, const fm3d_point2f *kpts1, int n1, const fm3d_point2f *kpts2, int n2,

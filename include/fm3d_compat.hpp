@@ -160,6 +160,8 @@ private:
     fm3d_settings s_;
 };
 
+class SingleCameraTriangulator;
+
 // DescriptorsMatcher (descriptorsmatcher.h:39-111)
 class DescriptorsMatcher {
 public:
@@ -180,6 +182,12 @@ public:
                                         tmp.data(), &n));
         matches.insert(matches.end(), tmp.begin(), tmp.begin() + n);
     }
+    // compareWithNNDR over the train keypoints within maxPx pixels of each query keypoint's epipolar
+    // line (fm3d_match_nndr_guided; no reference counterpart).  The pose is the one the triangulator
+    // installed with setg12 on this matcher's device; kpts_a / kpts_b: one keypoint per descriptor row.
+    inline void compareWithNNDRGuided(double epsilon, double maxPx, const SingleCameraTriangulator& triangulator,
+                                      std::vector<DMatch>& matches, const std::vector<KeyPoint>& kpts_a,
+                                      const std::vector<KeyPoint>& kpts_b, const DescMat& A, const DescMat& B);
 
 private:
     static void require_same(const DescMat& A, const DescMat& B) {
@@ -252,6 +260,25 @@ private:
     std::vector<fm3d_point2f> kp1_, kp2_;
     std::vector<DMatch> matches_;
 };
+
+inline void DescriptorsMatcher::compareWithNNDRGuided(double epsilon, double maxPx,
+                                                      const SingleCameraTriangulator& triangulator,
+                                                      std::vector<DMatch>& matches, const std::vector<KeyPoint>& kpts_a,
+                                                      const std::vector<KeyPoint>& kpts_b, const DescMat& A,
+                                                      const DescMat& B) {
+    require_same(A, B);
+    if (&triangulator.device() != &d_) throw Error(FM3D_ERR_INVALID, "the triangulator's pose lives on another device");
+    if ((int)kpts_a.size() != A.rows || (int)kpts_b.size() != B.rows)
+        throw Error(FM3D_ERR_INVALID, "one keypoint per descriptor row");
+    std::vector<fm3d_point2f> k1(kpts_a.size()), k2(kpts_b.size());
+    for (size_t i = 0; i < kpts_a.size(); i++) k1[i] = fm3d_point2f{kpts_a[i].pt.x, kpts_a[i].pt.y};
+    for (size_t i = 0; i < kpts_b.size(); i++) k2[i] = fm3d_point2f{kpts_b[i].pt.x, kpts_b[i].pt.y};
+    std::vector<DMatch> tmp(A.rows > 0 ? A.rows : 1);
+    int n = 0;
+    check(d_.ctx(), fm3d_match_nndr_guided(d_.ctx(), A.data, A.rows, B.data, B.rows, A.cols, A.type, k1.data(),
+                                           k2.data(), epsilon, maxPx, tmp.data(), &n));
+    matches.insert(matches.end(), tmp.begin(), tmp.begin() + n);
+}
 
 // NormalOptimizer (normaloptimizer.h:43-59), hot-path methods
 class NormalOptimizer {
