@@ -46,6 +46,7 @@ EXPORTS = (
     "fm3d_mser_detect", "fm3d_mser_detect_batch", "fm3d_mser_regions", "fm3d_pipeline_submit_dlt", "fm3d_pipeline_submit_dlt_pair",
     "fm3d_pipeline_submit_ncc", "fm3d_pipeline_wait_ncc", "fm3d_pipeline_wait_dlt", "fm3d_device_count",
     "fm3d_epipolar_matrix", "fm3d_epipolar_lines", "fm3d_knn2_guided", "fm3d_match_nndr_guided",
+    "fm3d_match_mutual", "fm3d_match_mutual_guided",
 )
 
 
@@ -87,6 +88,7 @@ class Settings(ctypes.Structure):
         ("lmReduction", ctypes.c_int),
         ("dltSolver", ctypes.c_int),
         ("guidedMatchPx", ctypes.c_double),
+        ("crossCheck", ctypes.c_int),
     ]
 
     @staticmethod
@@ -329,6 +331,46 @@ class DescriptorsMatcher:
                                                     a.shape[1], _desc_type(a, self.binary), _vp(k1), _vp(k2),
                                                     ctypes.c_double(epsilon), ctypes.c_double(max_px), _vp(out),
                                                     ctypes.byref(n)))
+        new = out[:n.value].copy()
+        return new if matches is None else np.concatenate([matches, new])
+
+    def compareWithNNDRMutual(self, epsilon: float, desc_a: np.ndarray, desc_b: np.ndarray, mode: int = 1,
+                              matches: np.ndarray | None = None) -> np.ndarray:
+        """compareWithNNDR with the cross-check (fm3d_match_mutual): mode 1 keeps a match (i, j) only
+        when query i is also the nearest query of train row j; mode 2 also asks row j's two nearest
+        queries to pass the ratio test.  New matches are appended to `matches`."""
+        a = np.ascontiguousarray(desc_a)
+        b = np.ascontiguousarray(desc_b)
+        if mode not in (1, 2):
+            raise Fm3dError(ERR_INVALID, "mode must be 1 (mutual nearest) or 2 (symmetric ratio)")
+        out = np.zeros(max(a.shape[0], 1), dtype=DMATCH)
+        n = ctypes.c_int(0)
+        self.ctx.check(lib().fm3d_match_mutual(self.ctx.handle, _vp(a), a.shape[0], _vp(b), b.shape[0], a.shape[1],
+                                               _desc_type(a, self.binary), ctypes.c_double(epsilon), int(mode),
+                                               _vp(out), ctypes.byref(n)))
+        new = out[:n.value].copy()
+        return new if matches is None else np.concatenate([matches, new])
+
+    def compareWithNNDRMutualGuided(self, epsilon: float, desc_a: np.ndarray, desc_b: np.ndarray, kp1: np.ndarray,
+                                    kp2: np.ndarray, max_px: float, mode: int = 1,
+                                    matches: np.ndarray | None = None) -> np.ndarray:
+        """compareWithNNDRMutual over the pairs that pass knn_match_guided's gate, in both directions
+        (fm3d_match_mutual_guided)."""
+        a = np.ascontiguousarray(desc_a)
+        b = np.ascontiguousarray(desc_b)
+        k1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
+        k2 = np.ascontiguousarray(kp2, dtype=np.float32).reshape(-1, 2)
+        if k1.shape[0] != a.shape[0] or k2.shape[0] != b.shape[0]:
+            raise ValueError("one keypoint per descriptor row")
+        _check_max_px(max_px)
+        if mode not in (1, 2):
+            raise Fm3dError(ERR_INVALID, "mode must be 1 (mutual nearest) or 2 (symmetric ratio)")
+        out = np.zeros(max(a.shape[0], 1), dtype=DMATCH)
+        n = ctypes.c_int(0)
+        self.ctx.check(lib().fm3d_match_mutual_guided(self.ctx.handle, _vp(a), a.shape[0], _vp(b), b.shape[0],
+                                                      a.shape[1], _desc_type(a, self.binary), _vp(k1), _vp(k2),
+                                                      ctypes.c_double(epsilon), ctypes.c_double(max_px), int(mode),
+                                                      _vp(out), ctypes.byref(n)))
         new = out[:n.value].copy()
         return new if matches is None else np.concatenate([matches, new])
 

@@ -113,6 +113,8 @@ struct fm3d_ctx {
     // the guided matchers' gate (fm3d_kernels.h EpiGate): query lines (float4) and train (u, v)
     DevBuf gLines, gUV;
     bool gateStaged = false;  // they belong to the staged pair's keypoints under the current g12
+    // the cross-check's reverse search (KnnSide): allocated only when it runs
+    DevBuf rCq, rCt, rA8, rB8, rPartIdx, rPartKey, rPairs, rIdx, rKey, rFkey;
     bool specU8 = false;      // the staged float rows went to the u8 matcher before their flag was read
     // SURF detection / description
     DevBuf sfImg, sfSum, sfDet, sfTr, sfLayers, sfMids, sfCand, sfCount, sfSortTmp, sfFlag, sfPos, sfKp, sfKin, sfSrc,
@@ -542,20 +544,27 @@ int make_lookback(fm3d_ctx* c, int nBlocks, fm3d::LookBack* lb) {
     return FM3D_OK;
 }
 
-// compactOut / compactCount (the pipeline): NNDR, the parts' merge (int keys) and the stable
-// compaction of the kept matches in one launch (launch_nndr_compact); else the NNDR flags and
-// candidates in c->flag / c->cand
-// gate (the guided matchers, fm3d_kernels.h EpiGate): every type takes its gated kernels
-int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int queryOffset, bool wantKnn,
-              fm3d_dmatch* compactOut = nullptr, int* compactCount = nullptr, const fm3d::EpiGate* gate = nullptr) {
-    const bool fuse = compactOut != nullptr && !wantKnn;
-    int mergeParts = 1;  // > 1: the parts' lists are merged by launch_nndr_compact
-    HIPCHK(c, c->idx.ensure((size_t)nA * 2 * sizeof(int) + 16));
-    HIPCHK(c, c->key.ensure((size_t)nA * 2 * sizeof(int) + 16));
-    HIPCHK(c, c->fkey.ensure((size_t)nA * 2 * sizeof(float) + 16));
-    HIPCHK(c, c->cand.ensure((size_t)nA * sizeof(fm3d_dmatch) + 16));
-    HIPCHK(c, c->flag.ensure((size_t)nA * sizeof(int) + 16));
-    if (wantKnn) HIPCHK(c, c->knnOut.ensure((size_t)nA * 2 * sizeof(fm3d_dmatch) + 16));
+// The buffers of one k = 2 search: the forward search's are the context's own; the cross-check's
+// reverse search runs the same routes with the two sides' rows swapped and its
+// own constants, unpacked / pair copies, part lists and top-2 lists.
+struct KnnSide {
+    DevBuf &A, &B;              // query rows, train rows (as stage_descriptors left them)
+    DevBuf &cqA, &ctB;          // u8: query constants, packed train constants
+    DevBuf &A8, &B8;            // 256-bit rows unpacked: queries 0/1, train rows -1/+1
+    DevBuf &partIdx, &partKey;  // the parts' lists
+    DevBuf &bPairs;             // float rows: the row-pair copy of the train side
+    DevBuf &idx, &key, &fkey;   // the merged top-2 lists
+};
+
+// the k = 2 search of nA query rows over nB train rows into b.idx / b.key / b.fkey.  deferMerge: the
+// int8-MFMA routes leave their parts' lists in b.partIdx / b.partKey and set *mergeParts (the fused
+// NNDR launch merges them).  gate (fm3d_kernels.h EpiGate): every type takes its gated kernels.
+int knn2_search(fm3d_ctx* c, const KnnSide& b, int nA, int nB, int type, int dimPad, bool deferMerge, int* mergeParts,
+                const fm3d::EpiGate* gate) {
+    *mergeParts = 1;
+    HIPCHK(c, b.idx.ensure((size_t)nA * 2 * sizeof(int) + 16));
+    HIPCHK(c, b.key.ensure((size_t)nA * 2 * sizeof(int) + 16));
+    HIPCHK(c, b.fkey.ensure((size_t)nA * 2 * sizeof(float) + 16));
     if (c->nCU <= 0) {
         int n = 0;
         HIPCHK(c, hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device));
@@ -563,29 +572,29 @@ int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int
     }
     if (type == FM3D_DESC_U8) {
         const int nAPad = nA, nBPad = nB;
-        HIPCHK(c, c->cqA.ensure((size_t)(nAPad + 1) * sizeof(int)));
-        HIPCHK(c, c->ctB.ensure((size_t)(nBPad + 1) * sizeof(int)));
-        fm3d::launch_rowconst_u8(c->A.as<uint8_t>(), nA, c->B.as<uint8_t>(), nB, dimPad, c->cqA.as<int>(),
-                                 c->ctB.as<int>(), c->stream);
+        HIPCHK(c, b.cqA.ensure((size_t)(nAPad + 1) * sizeof(int)));
+        HIPCHK(c, b.ctB.ensure((size_t)(nBPad + 1) * sizeof(int)));
+        fm3d::launch_rowconst_u8(b.A.as<uint8_t>(), nA, b.B.as<uint8_t>(), nB, dimPad, b.cqA.as<int>(),
+                                 b.ctB.as<int>(), c->stream);
         const int parts = fm3d::knn2_u8_parts(nA, nB, c->nCU, fm3d::knn2_i8_queries_per_block(dimPad, 0),
                                               fm3d::knn2_i8_tile_rows(dimPad, 0));
         if (parts > 1) {
-            HIPCHK(c, c->partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
-            HIPCHK(c, c->partKey.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, b.partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, b.partKey.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
         }
-        if (fuse && parts > 1) mergeParts = parts;
-        fm3d::launch_knn2_i8(c->A.as<uint8_t>(), nA, c->B.as<uint8_t>(), nB, dimPad, 0, c->cqA.as<int>(),
-                             c->ctB.as<int>(), parts, c->partIdx.as<int>(), c->partKey.as<int>(), c->idx.as<int>(),
-                             c->key.as<int>(), c->stream, mergeParts > 1, gate);
+        if (deferMerge && parts > 1) *mergeParts = parts;
+        fm3d::launch_knn2_i8(b.A.as<uint8_t>(), nA, b.B.as<uint8_t>(), nB, dimPad, 0, b.cqA.as<int>(),
+                             b.ctB.as<int>(), parts, b.partIdx.as<int>(), b.partKey.as<int>(), b.idx.as<int>(),
+                             b.key.as<int>(), c->stream, *mergeParts > 1, gate);
     } else if (type == FM3D_DESC_F32 && gate) {
         // no bf16 prefilter here (its bound knows nothing of the gate): the exact scan of the rows inside it
         const int parts = fm3d::knn2_parts(nA, nB, dimPad, c->nCU);
         if (parts > 1) {
-            HIPCHK(c, c->partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
-            HIPCHK(c, c->partKey.ensure((size_t)parts * nA * 2 * sizeof(float) + 16));
+            HIPCHK(c, b.partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, b.partKey.ensure((size_t)parts * nA * 2 * sizeof(float) + 16));
         }
-        fm3d::launch_knn2_f32_gated(c->A.as<float>(), nA, c->B.as<float>(), nB, dimPad, parts, c->partIdx.as<int>(),
-                                    c->partKey.as<float>(), c->idx.as<int>(), c->fkey.as<float>(), *gate, c->stream);
+        fm3d::launch_knn2_f32_gated(b.A.as<float>(), nA, b.B.as<float>(), nB, dimPad, parts, b.partIdx.as<int>(),
+                                    b.partKey.as<float>(), b.idx.as<int>(), b.fkey.as<float>(), *gate, c->stream);
     } else if (type == FM3D_DESC_F32 && (dimPad == 64 || dimPad == 128) && nB >= 64 &&
                (long long)nA * nB >= (1LL << 22) && f32_mfma()) {
         // float rows (SURF): the bf16 MFMA prefilter lists each query's possible top-2 rows, whose exact
@@ -598,8 +607,8 @@ int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int
         bool fused = !(fe && fe[0] == '0');
         int nResc = 0;
         for (;;) {
-            fm3d::launch_knn2_f32_mfma(c->A.as<float>(), nA, c->B.as<float>(), nB, dimPad, parts, fused, c->f32Work.p,
-                                       c->idx.as<int>(), c->fkey.as<float>(), c->stream);
+            fm3d::launch_knn2_f32_mfma(b.A.as<float>(), nA, b.B.as<float>(), nB, dimPad, parts, fused, c->f32Work.p,
+                                       b.idx.as<int>(), b.fkey.as<float>(), c->stream);
             HIPCHK(c, hipMemcpyAsync(&nResc, fm3d::knn2_f32_mfma_rescan_count(c->f32Work.p, nA, nB, dimPad, parts),
                                      sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -608,60 +617,103 @@ int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int
         }
         if (nResc > 0 && nResc <= nA / 8) {
             // the queries whose bound held more rows than the candidate list: an exact wave-per-query scan
-            fm3d::launch_knn2_f32_mfma_rescan(c->A.as<float>(), c->B.as<float>(), nB, dimPad, c->f32Work.p, nA, parts,
-                                              nResc, c->idx.as<int>(), c->fkey.as<float>(), c->stream);
+            fm3d::launch_knn2_f32_mfma_rescan(b.A.as<float>(), b.B.as<float>(), nB, dimPad, c->f32Work.p, nA, parts,
+                                              nResc, b.idx.as<int>(), b.fkey.as<float>(), c->stream);
         } else if (nResc > 0) {
             // descriptors with no margin between neighbours (e.g. uniform noise in high dimension):
             // the full exact scan for every query
             const int p2 = fm3d::knn2_parts(nA, nB, dimPad, c->nCU);
             if (p2 > 1) {
-                HIPCHK(c, c->partIdx.ensure((size_t)p2 * nA * 2 * sizeof(int) + 16));
-                HIPCHK(c, c->partKey.ensure((size_t)p2 * nA * 2 * sizeof(float) + 16));
+                HIPCHK(c, b.partIdx.ensure((size_t)p2 * nA * 2 * sizeof(int) + 16));
+                HIPCHK(c, b.partKey.ensure((size_t)p2 * nA * 2 * sizeof(float) + 16));
             }
-            HIPCHK(c, c->bPairs.ensure(fm3d::knn2_f32_pairs_bytes(nB, dimPad) + 16));
-            fm3d::launch_knn2_f32(c->A.as<float>(), nA, c->B.as<float>(), nB, dimPad, p2, c->partIdx.as<int>(),
-                                  c->partKey.as<float>(), c->bPairs.as<float>(), c->idx.as<int>(), c->fkey.as<float>(),
+            HIPCHK(c, b.bPairs.ensure(fm3d::knn2_f32_pairs_bytes(nB, dimPad) + 16));
+            fm3d::launch_knn2_f32(b.A.as<float>(), nA, b.B.as<float>(), nB, dimPad, p2, b.partIdx.as<int>(),
+                                  b.partKey.as<float>(), b.bPairs.as<float>(), b.idx.as<int>(), b.fkey.as<float>(),
                                   c->stream);
         }
     } else if (type == FM3D_DESC_F32) {
         const int parts = (dimPad == 64 || dimPad == 128) ? fm3d::knn2_parts(nA, nB, dimPad, c->nCU) : 1;
         if (parts > 1) {
-            HIPCHK(c, c->partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
-            HIPCHK(c, c->partKey.ensure((size_t)parts * nA * 2 * sizeof(float) + 16));
+            HIPCHK(c, b.partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, b.partKey.ensure((size_t)parts * nA * 2 * sizeof(float) + 16));
         }
-        HIPCHK(c, c->bPairs.ensure(fm3d::knn2_f32_pairs_bytes(nB, dimPad) + 16));
-        fm3d::launch_knn2_f32(c->A.as<float>(), nA, c->B.as<float>(), nB, dimPad, parts, c->partIdx.as<int>(),
-                              c->partKey.as<float>(), c->bPairs.as<float>(), c->idx.as<int>(), c->fkey.as<float>(),
+        HIPCHK(c, b.bPairs.ensure(fm3d::knn2_f32_pairs_bytes(nB, dimPad) + 16));
+        fm3d::launch_knn2_f32(b.A.as<float>(), nA, b.B.as<float>(), nB, dimPad, parts, b.partIdx.as<int>(),
+                              b.partKey.as<float>(), b.bPairs.as<float>(), b.idx.as<int>(), b.fkey.as<float>(),
                               c->stream);
     } else if (dimPad == 32 && bits_mfma()) {
         // 256-bit rows (ORB): unpacked to int8 and matched on the int8 MFMA kernel (exact integer
         // Hamming distances popc(b) - a.b', same ranking rule)
-        HIPCHK(c, c->A8.ensure((size_t)nA * 256 + 16));
-        HIPCHK(c, c->B8.ensure((size_t)nB * 256 + 16));
-        HIPCHK(c, c->ctB.ensure((size_t)(nB + 1) * sizeof(int)));
-        fm3d::launch_unpack_bits(c->A.as<uint8_t>(), nA, c->B.as<uint8_t>(), nB, c->A8.as<uint8_t>(),
-                                 c->B8.as<uint8_t>(), c->ctB.as<int>(), c->stream);
+        HIPCHK(c, b.A8.ensure((size_t)nA * 256 + 16));
+        HIPCHK(c, b.B8.ensure((size_t)nB * 256 + 16));
+        HIPCHK(c, b.ctB.ensure((size_t)(nB + 1) * sizeof(int)));
+        fm3d::launch_unpack_bits(b.A.as<uint8_t>(), nA, b.B.as<uint8_t>(), nB, b.A8.as<uint8_t>(),
+                                 b.B8.as<uint8_t>(), b.ctB.as<int>(), c->stream);
         const int parts = fm3d::knn2_u8_parts(nA, nB, c->nCU, fm3d::knn2_i8_queries_per_block(256, 1),
                                               fm3d::knn2_i8_tile_rows(256, 1));
         if (parts > 1) {
-            HIPCHK(c, c->partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
-            HIPCHK(c, c->partKey.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, b.partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, b.partKey.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
         }
-        if (fuse && parts > 1) mergeParts = parts;
-        fm3d::launch_knn2_i8(c->A8.as<uint8_t>(), nA, c->B8.as<uint8_t>(), nB, 256, 1, nullptr, c->ctB.as<int>(),
-                             parts, c->partIdx.as<int>(), c->partKey.as<int>(), c->idx.as<int>(), c->key.as<int>(),
-                             c->stream, mergeParts > 1, gate);
+        if (deferMerge && parts > 1) *mergeParts = parts;
+        fm3d::launch_knn2_i8(b.A8.as<uint8_t>(), nA, b.B8.as<uint8_t>(), nB, 256, 1, nullptr, b.ctB.as<int>(),
+                             parts, b.partIdx.as<int>(), b.partKey.as<int>(), b.idx.as<int>(), b.key.as<int>(),
+                             c->stream, *mergeParts > 1, gate);
     } else {
         const int parts = fm3d::knn2_parts(nA, nB, dimPad, c->nCU);
         if (parts > 1) {
-            HIPCHK(c, c->partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
-            HIPCHK(c, c->partKey.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, b.partIdx.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
+            HIPCHK(c, b.partKey.ensure((size_t)parts * nA * 2 * sizeof(int) + 16));
         }
-        fm3d::launch_knn2_bits(c->A.as<uint8_t>(), nA, c->B.as<uint8_t>(), nB, dimPad, parts, c->partIdx.as<int>(),
-                               c->partKey.as<int>(), c->idx.as<int>(), c->key.as<int>(), c->stream, gate);
+        fm3d::launch_knn2_bits(b.A.as<uint8_t>(), nA, b.B.as<uint8_t>(), nB, dimPad, parts, b.partIdx.as<int>(),
+                               b.partKey.as<int>(), b.idx.as<int>(), b.key.as<int>(), c->stream, gate);
     }
     HIPCHK(c, hipGetLastError());
-    if (fuse) {
+    return FM3D_OK;
+}
+
+// compactOut / compactCount (the pipeline): NNDR, the parts' merge (int keys) and the stable
+// compaction of the kept matches in one launch (launch_nndr_compact); else the NNDR flags and
+// candidates in c->flag / c->cand
+// gate (the guided matchers, fm3d_kernels.h EpiGate): every type takes its gated kernels
+// crossCheck 1 / 2 (with compactOut only): the reverse search over the same rows
+// (and the same gate, transposed), then the NNDR launch's mutual form; 0 adds nothing
+int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, double eps, int queryOffset, bool wantKnn,
+              fm3d_dmatch* compactOut = nullptr, int* compactCount = nullptr, const fm3d::EpiGate* gate = nullptr,
+              int crossCheck = 0) {
+    const bool fuse = compactOut != nullptr && !wantKnn;
+    if (crossCheck && !fuse) return fail(c, FM3D_ERR_INVALID, "the cross-check needs the compacted output");
+    int mergeParts = 1;  // > 1: the parts' lists are merged by launch_nndr_compact
+    HIPCHK(c, c->idx.ensure((size_t)nA * 2 * sizeof(int) + 16));
+    HIPCHK(c, c->key.ensure((size_t)nA * 2 * sizeof(int) + 16));
+    HIPCHK(c, c->fkey.ensure((size_t)nA * 2 * sizeof(float) + 16));
+    HIPCHK(c, c->cand.ensure((size_t)nA * sizeof(fm3d_dmatch) + 16));
+    HIPCHK(c, c->flag.ensure((size_t)nA * sizeof(int) + 16));
+    if (wantKnn) HIPCHK(c, c->knnOut.ensure((size_t)nA * 2 * sizeof(fm3d_dmatch) + 16));
+    {
+        const KnnSide fwd{c->A, c->B, c->cqA, c->ctB, c->A8, c->B8, c->partIdx, c->partKey, c->bPairs, c->idx, c->key, c->fkey};
+        int r;
+        if ((r = knn2_search(c, fwd, nA, nB, type, dimPad, fuse, &mergeParts, gate))) return r;
+    }
+    if (crossCheck) {
+        // rev[j]: train row j's two nearest queries.  With a gate both searches rank the same
+        // admissible pairs: the reverse kernels evaluate the forward predicate with the sides swapped
+        const KnnSide rev{c->B, c->A, c->rCq, c->rCt, c->rA8, c->rB8, c->rPartIdx, c->rPartKey, c->rPairs, c->rIdx, c->rKey, c->rFkey};
+        fm3d::EpiGate rg{};
+        if (gate) {
+            rg = *gate;
+            rg.transposed = true;
+        }
+        int r, revParts = 1;
+        if ((r = knn2_search(c, rev, nB, nA, type, dimPad, false, &revParts, gate ? &rg : nullptr))) return r;
+        fm3d::LookBack lb;
+        if ((r = make_lookback(c, fm3d::nndr_compact_blocks(nA), &lb))) return r;
+        const fm3d::MutualCheck mc{c->rIdx.as<int>(), c->rKey.as<int>(), c->rFkey.as<float>(), crossCheck};
+        fm3d::launch_nndr_mutual_compact(type, c->idx.as<int>(), c->key.as<int>(), c->fkey.as<float>(),
+                                         c->partIdx.as<int>(), c->partKey.as<int>(), mergeParts, nA, eps, queryOffset,
+                                         mc, compactOut, compactCount, lb, c->stream);
+    } else if (fuse) {
         fm3d::LookBack lb;
         int r;
         if ((r = make_lookback(c, fm3d::nndr_compact_blocks(nA), &lb))) return r;
@@ -1772,6 +1824,7 @@ int fm3d_ctx_create(const fm3d_settings* s, int device, fm3d_ctx** out) {
     *out = nullptr;
     if (s->dltSolver != 0 && s->dltSolver != 1) return FM3D_ERR_INVALID;  // cvSVD or the legacy Jacobi
     if (!(s->guidedMatchPx >= 0. && s->guidedMatchPx <= DBL_MAX)) return FM3D_ERR_INVALID;  // 0 = off; NaN fails
+    if (s->crossCheck < 0 || s->crossCheck > 2) return FM3D_ERR_INVALID;  // off, mutual nearest, symmetric ratio
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return FM3D_ERR_HIP;
     if (device < 0 || device >= n) return FM3D_ERR_INVALID;
@@ -1814,6 +1867,7 @@ void fm3d_ctx_destroy(fm3d_ctx* c) {
                       &c->lmInfo, &c->lmNfev, &c->lmMdat, &c->lmQueue, &c->lmStat,
                       &c->slab, &c->slabI1,
                       &c->records, &c->recTmp, &c->recFlag, &c->lmProj, &c->partIdx, &c->partKey, &c->bPairs, &c->f32Work, &c->A8, &c->B8, &c->u8Flag, &c->gLines, &c->gUV,
+                      &c->rCq, &c->rCt, &c->rA8, &c->rB8, &c->rPartIdx, &c->rPartKey, &c->rPairs, &c->rIdx, &c->rKey, &c->rFkey,
                       &c->sfImg, &c->sfSum, &c->sfDet, &c->sfTr, &c->sfLayers, &c->sfMids, &c->sfCand, &c->sfCount,
                       &c->sfSortTmp, &c->sfFlag, &c->sfPos, &c->sfKp, &c->sfKin, &c->sfSrc, &c->sfDesc, &c->sfDW, &c->sfAng,
                       &c->orbPyr, &c->orbTab, &c->orbLev, &c->orbMap, &c->orbFlag, &c->orbPos, &c->orbKp, &c->orbR,
@@ -1966,6 +2020,51 @@ int fm3d_match_nndr_guided(fm3d_ctx* c, const void* descA, int nA, const void* d
     if (n) HIPCHK(c, hipMemcpy(matches, c->matches.p, (size_t)n * sizeof(fm3d_dmatch), hipMemcpyDeviceToHost));
     *nMatches = n;
     return FM3D_OK;
+}
+
+namespace {
+// the compacted matches of a cross-checked call (c->matches, c->count) to the host
+int mutual_download(fm3d_ctx* c, fm3d_dmatch* matches, int* nMatches) {
+    int n = 0;
+    HIPCHK(c, hipMemcpyAsync(&n, c->count.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n) HIPCHK(c, hipMemcpy(matches, c->matches.p, (size_t)n * sizeof(fm3d_dmatch), hipMemcpyDeviceToHost));
+    *nMatches = n;
+    return FM3D_OK;
+}
+}  // namespace
+
+int fm3d_match_mutual(fm3d_ctx* c, const void* descA, int nA, const void* descB, int nB, int dim, int type,
+                      double epsilon, int mode, fm3d_dmatch* matches, int* nMatches) {
+    if (!c || !nMatches || (!descA && nA) || (!descB && nB) || (!matches && nA))
+        return fail(c, FM3D_ERR_INVALID, "null argument");
+    if (mode != 1 && mode != 2) return fail(c, FM3D_ERR_INVALID, "mode must be 1 (mutual nearest) or 2 (symmetric ratio)");
+    hipSetDevice(c->device);
+    int t, dp, r;
+    if ((r = stage_descriptors(c, descA, nA, descB, nB, dim, type, &t, &dp))) return r;
+    if ((r = ensure_scan_tmp(c, nA))) return r;
+    HIPCHK(c, c->matches.ensure((size_t)(nA + 1) * sizeof(fm3d_dmatch)));
+    if ((r = run_match(c, nA, nB, t, dp, epsilon, 0, false, c->matches.as<fm3d_dmatch>(), c->count.as<int>(), nullptr,
+                       mode)))
+        return r;
+    return mutual_download(c, matches, nMatches);
+}
+
+int fm3d_match_mutual_guided(fm3d_ctx* c, const void* descA, int nA, const void* descB, int nB, int dim, int type,
+                             const fm3d_point2f* kpts1, const fm3d_point2f* kpts2, double epsilon, double maxPx,
+                             int mode, fm3d_dmatch* matches, int* nMatches) {
+    if (!c || !nMatches || (!descA && nA) || (!descB && nB) || (!matches && nA) || (!kpts1 && nA) || (!kpts2 && nB))
+        return fail(c, FM3D_ERR_INVALID, "null argument");
+    if (mode != 1 && mode != 2) return fail(c, FM3D_ERR_INVALID, "mode must be 1 (mutual nearest) or 2 (symmetric ratio)");
+    int t, dp, r;
+    fm3d::EpiGate gate{};
+    if ((r = stage_guided(c, descA, nA, descB, nB, dim, type, kpts1, kpts2, maxPx, &t, &dp, &gate))) return r;
+    if ((r = ensure_scan_tmp(c, nA))) return r;
+    HIPCHK(c, c->matches.ensure((size_t)(nA + 1) * sizeof(fm3d_dmatch)));
+    if ((r = run_match(c, nA, nB, t, dp, epsilon, 0, false, c->matches.as<fm3d_dmatch>(), c->count.as<int>(), &gate,
+                       mode)))
+        return r;
+    return mutual_download(c, matches, nMatches);
 }
 
 int fm3d_g12_from_poses(const fm3d_settings* s, const double T1[3], const double T2[3], const double r1[3],
@@ -2206,7 +2305,7 @@ int pipeline_front(fm3d_ctx* c) {
     if ((r = ensure_scan_tmp(c, nA))) return r;
     HIPCHK(c, c->matches.ensure((size_t)(nA + 1) * sizeof(fm3d_dmatch)));
     if ((r = run_match(c, nA, nB, c->stType, c->stDimPad, c->s.nndrEpsilon, c->stQueryOffset, false,
-                       c->matches.as<fm3d_dmatch>(), cnt + 0, guided ? &gate : nullptr)))
+                       c->matches.as<fm3d_dmatch>(), cnt + 0, guided ? &gate : nullptr, c->s.crossCheck)))
         return r;
     // the stage boundaries (ev[3]: match + NNDR done, ev[5]: DLT done) only when asked for: a timed
     // event between two launches costs the C2 step 4-10 us of gap (rocprofv3 trace, round 5);
@@ -2527,6 +2626,9 @@ int fm3d_internal_memory_need(fm3d_ctx* c, int64_t nA, int64_t nB, int dim, int 
     const size_t rowWork = 256 + (type == FM3D_DESC_F32 ? (size_t)dim * 4 : 0);  // u8 / unpacked / pair copies
     need += (size_t)(nA + nB) * (rowIn + rowWork) + (size_t)nB * 64;
     if (c->s.guidedMatchPx > 0.) need += (size_t)nA * 16 + (size_t)nB * 8;  // the gate's lines and (u, v)
+    // the cross-check's reverse search: unpacked / pair copies of both sides, row constants, the
+    // train rows' top-2 lists and 16 parts of them
+    if (c->s.crossCheck != 0) need += (size_t)(nA + nB) * (rowWork + 8) + (size_t)nB * (24 + 16 * 16);
     need += (size_t)nA * 1536;  // per query: top-2 lists + 16 parts, matches, points, masks, LM arrays, records
     need += (size_t)width * height * 4 + ((size_t)16 << 20);  // pyramids with guards, small buffers
     *bytes = need;

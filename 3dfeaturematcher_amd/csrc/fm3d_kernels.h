@@ -119,6 +119,10 @@ struct EpiGate {
     const float4* lines;  // nA query lines
     const float2* uv;     // nB undistorted train keypoints
     double tau;           // maxPx * 2 / (fx + fy)
+    // the reverse search of the cross-check: the launch's queries are the train
+    // rows (they own uv) and its train rows the queries (they own lines); the predicate, its
+    // operands and their order are the forward gate's
+    bool transposed = false;
 };
 // lines[i] of kp1[i] (n1 queries) under E (row-major 3 x 3) and uv[j] = undistort1(kp2[j]) (n2 train
 // rows), both rounded to float, in one launch
@@ -380,6 +384,21 @@ void launch_nndr_compact(int type, const int* idx, const int* key, const float* 
                          const int* partKey, int parts, int nA, double eps, int queryOffset, fm3d_dmatch* out,
                          int* count, const LookBack& lb, hipStream_t s);
 int nndr_compact_blocks(int nA);
+// The cross-check on top of launch_nndr_compact: query q with forward best row j
+// is kept iff the NNDR rule holds, rIdx[2 j] == q (the merged top-2 of the reverse search: for
+// every train row its two nearest queries, order (distance, queryIdx)) and, mode 2, row j's two
+// reverse neighbours exist and pass the ratio rule with the same epsilon.  rKey (int keys: u8,
+// bits) / rFkey (f32) hold the reverse lists' keys of the forward lists' kind.
+struct MutualCheck {
+    const int* rIdx;
+    const int* rKey;
+    const float* rFkey;
+    int mode;  // 1 mutual nearest, 2 symmetric ratio
+};
+void launch_nndr_mutual_compact(int type, const int* idx, const int* key, const float* fkey, const int* partIdx,
+                                const int* partKey, int parts, int nA, double eps, int queryOffset,
+                                const MutualCheck& mc, fm3d_dmatch* out, int* count, const LookBack& lb,
+                                hipStream_t s);
 // setKeypoints + triangulate with the compaction of the inliers: out (P x 3), srcIdx (P), *count = P;
 // mask (K) as launch_triangulate
 void launch_triangulate_compact(const TriParams& p, double* out, int* srcIdx, int* count, const LookBack& lb,

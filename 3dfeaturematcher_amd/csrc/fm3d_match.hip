@@ -166,15 +166,20 @@ __global__ void unpack_bits_kernel(const uint32_t* __restrict__ A, int nA, const
 // GATE: the guided matcher (fm3d_kernels.h EpiGate).  A lane's queries' lines stay in registers,
 // the tile's (u, v) are staged in LDS next to ctl, and the epilogue zeroes the packed key ("no row")
 // of a pair outside the gate; ranking, merges and outputs are the ungated kernel's.
-template <bool GATE>
-struct GateArgs {};
-template <>
-struct GateArgs<true> {
+// GATE is kGateNone, kGateLane (the forward search: lines on the lane, (u, v) on the tile) or
+// kGateTile (the cross-check's reverse search, DESIGN.md §3.1c: a lane's queries are train rows of
+// the pair, so it keeps their (u, v) as doubles, and the tile's rows are the pair's queries, whose
+// float4 lines are staged in LDS; the same expression on the same operands in the same order).
+constexpr int kGateNone = 0, kGateLane = 1, kGateTile = 2;
+template <int GATE>
+struct GateArgs {
     const float4* lines;
     const float2* uv;
     double tau;
 };
-template <int KS, bool BITS, int QG, int TR = kT, bool GATE = false>
+template <>
+struct GateArgs<kGateNone> {};
+template <int KS, bool BITS, int QG, int TR = kT, int GATE = kGateNone>
 __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __restrict__ A, int nA,
                                                            const uint8_t* __restrict__ B, int nB, int dimPad,
                                                            const int* __restrict__ cqA, const int* __restrict__ ctB,
@@ -188,7 +193,8 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
     const int tileBytes = TR * (KS ? 32 * KS : dimPad);
     unsigned char* tiles = smem;                              // 2 x tileBytes
     uint32_t* ctl = (uint32_t*)(smem + 2 * (size_t)tileBytes);  // 2 x TR packed row constants
-    float2* uvl = (float2*)(ctl + 2 * TR);                      // GATE: 2 x TR train (u, v)
+    float2* uvl = (float2*)(ctl + 2 * TR);                      // kGateLane: 2 x TR train (u, v)
+    float4* lnl = (float4*)(ctl + 2 * TR);                      // kGateTile: 2 x TR lines (16-byte aligned)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q0 = blockIdx.x * (kQ * QG) + wave * 32 * QG;
     const int half = lane >> 5;
@@ -220,7 +226,19 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
     }
     // GATE: this lane's query lines; a lane without a query passes no row
     double la[QG], lb[QG], lc[QG], tau = 0.;
-    if constexpr (GATE) {
+    double pu[QG], pv[QG];  // kGateTile: this lane's rows' (u, v); NaN (passes no line) without a row
+    if constexpr (GATE == kGateTile) {
+        tau = gate.tau;
+#pragma unroll
+        for (int g = 0; g < QG; g++) {
+            const int qrow = q0 + 32 * g + (lane & 31);
+            float2 w = make_float2(__builtin_nanf(""), __builtin_nanf(""));
+            if (qrow < nA) w = gate.uv[qrow];
+            pu[g] = (double)w.x;
+            pv[g] = (double)w.y;
+        }
+    }
+    if constexpr (GATE == kGateLane) {
         tau = gate.tau;
 #pragma unroll
         for (int g = 0; g < QG; g++) {
@@ -243,6 +261,7 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
     v4i pre[kPre];
     uint32_t preCt = 0;
     float2 preUV = make_float2(0.f, 0.f);
+    float4 preLn = make_float4(0.f, 0.f, 0.f, 0.f);
     auto load_tile = [&](int t) {
         // rows past nB only in the last tile: the others load without a per-chunk test
         const uint8_t* tb = B + (size_t)t * TR * rowBytes;
@@ -264,7 +283,9 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
         if (tid < TR) {
             const int j = t * TR + tid;
             preCt = (j < nB) ? (uint32_t)ctB[j] : 0u;
-            if constexpr (GATE) preUV = (j < nB) ? gate.uv[j] : make_float2(0.f, 0.f);
+            if constexpr (GATE == kGateLane) preUV = (j < nB) ? gate.uv[j] : make_float2(0.f, 0.f);
+            if constexpr (GATE == kGateTile)
+                preLn = (j < nB) ? gate.lines[j] : make_float4(0.f, 0.f, __builtin_inff(), 0.f);
         }
     };
     auto store_tile = [&](int buf) {
@@ -280,7 +301,8 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
         }
         if (tid < TR) {
             ctl[buf * TR + tid] = preCt;
-            if constexpr (GATE) uvl[buf * TR + tid] = preUV;
+            if constexpr (GATE == kGateLane) uvl[buf * TR + tid] = preUV;
+            if constexpr (GATE == kGateTile) lnl[buf * TR + tid] = preLn;
         }
     };
     struct Acc {
@@ -298,6 +320,7 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
         const unsigned char* tl = tiles + (size_t)buf * tileBytes;
         const uint32_t* ct = ctl + buf * TR;
         const float2* uvt = uvl + buf * TR;
+        const float4* lnt = lnl + buf * TR;
         // packed top-2 (largest) of this tile per query group, two chains (even / odd row blocks)
         // merged after the tile
         uint32_t p1[QG][2], p2[QG][2];
@@ -326,7 +349,29 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
             // tested against one per-lane limit (the row offsets stay compile-time constants)
             const int c = rb & 1;
             const int lim = nB - t * TR - 4 * half;
-            if constexpr (GATE) {
+            if constexpr (GATE == kGateTile) {
+                // row-major: a row's line is read and widened once for the QG groups
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const float4 w = lnt[row];
+                    const double a = (double)w.x, b = (double)w.y, cc = (double)w.z;
+                    const uint32_t ctr = ct[row];
+#pragma unroll
+                    for (int g = 0; g < QG; g++) {
+                        uint32_t v = ((uint32_t)acc.a[g][r] << kShift) + ctr;
+                        // the forward gate's expression: line of the pair's query, point of its train row
+                        const double d = __builtin_fabs(__builtin_fma(a, pu[g], b * pv[g]) + cc);
+                        bool in = d <= tau;  // false for NaN
+                        if (!decltype(fullc)::value) in = in && (rb * 32 + (r & 3) + 8 * (r >> 2) < lim);
+                        v = in ? v : 0u;
+                        p2[g][c] = med3u(p1[g][c], p2[g][c], v);
+                        p1[g][c] = umax(p1[g][c], v);
+                    }
+                }
+                return;
+            }
+            if constexpr (GATE == kGateLane) {
                 // row-major here: a row's (u, v) are read and widened once for the QG groups
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
@@ -683,12 +728,24 @@ __global__ void nndr_kernel(int type, const int* __restrict__ idx, const int* __
 // nndr_kernel with the parts' merge (knn2_int_merge's rule; int keys) and the stable compaction of the
 // kept matches in one launch (fm3d_kernels.h LookBack): the pipeline's a1 without two launches and
 // their round trips.  Block b's queries are b*256 .. b*256+255, b taken in launch order.
+// MUTUAL: the cross-check (fm3d_kernels.h MutualCheck) decided between the NNDR rule and the
+// compaction, against the merged lists of the reverse search.
+template <bool MUTUAL>
+struct MutualArgs {};
+template <>
+struct MutualArgs<true> {
+    const int* rIdx;
+    const int* rKey;
+    const float* rFkey;
+    int mode;
+};
+template <bool MUTUAL>
 __global__ __launch_bounds__(256) void nndr_compact_kernel(int type, const int* __restrict__ idx,
                                                            const int* __restrict__ key, const float* __restrict__ fkey,
                                                            const int* __restrict__ pIdx, const int* __restrict__ pKey,
                                                            int parts, int nA, double eps, int queryOffset,
                                                            fm3d_dmatch* __restrict__ out, int* __restrict__ count,
-                                                           LookBack lb) {
+                                                           LookBack lb, MutualArgs<MUTUAL> mu) {
     __shared__ int sBid, sEx, sWave[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) sBid = lookback_block_id(lb);
@@ -754,6 +811,28 @@ __global__ __launch_bounds__(256) void nndr_compact_kernel(int type, const int* 
         // descriptorsmatcher.cpp:121-128: size() >= 2 and distance0 <= epsilon * distance1 (double)
         keep = (i1 >= 0 && i2 >= 0) && ((double)d1 <= eps * (double)d2);
         cand = fm3d_dmatch{q + queryOffset, i1, 0, d1};
+        if constexpr (MUTUAL) {
+            if (keep) {
+                // row i1's nearest query is q (q: the index inside this context's query set, which is
+                // the whole set wherever the cross-check runs)
+                const int r1 = mu.rIdx[2 * (size_t)i1], r2 = mu.rIdx[2 * (size_t)i1 + 1];
+                keep = r1 == q;
+                if (keep && mu.mode == 2) {
+                    float e1, e2;
+                    if (type == FM3D_DESC_F32) {
+                        e1 = sqrtf(mu.rFkey[2 * (size_t)i1]);
+                        e2 = sqrtf(mu.rFkey[2 * (size_t)i1 + 1]);
+                    } else if (type == FM3D_DESC_U8) {
+                        e1 = sqrtf((float)mu.rKey[2 * (size_t)i1]);
+                        e2 = sqrtf((float)mu.rKey[2 * (size_t)i1 + 1]);
+                    } else {
+                        e1 = (float)mu.rKey[2 * (size_t)i1];
+                        e2 = (float)mu.rKey[2 * (size_t)i1 + 1];
+                    }
+                    keep = r2 >= 0 && ((double)e1 <= eps * (double)e2);
+                }
+            }
+        }
     }
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) sWave[wave] = __popcll(bal);
@@ -1145,7 +1224,33 @@ __device__ inline bool gate_pass(double a, double b, double c, float2 w, double 
     return __builtin_fabs(__builtin_fma(a, (double)w.x, b * (double)w.y) + c) <= tau;  // false for NaN
 }
 
+// The thread's side of the gate in registers, the scanned row's side loaded per row.  TRANS (the
+// cross-check's reverse search): the thread's row is a train row of the pair, so it holds (u, v)
+// and each scanned row brings its line; gate_pass sees the forward gate's operands either way.
+template <bool TRANS>
+struct GateLane {
+    double la = 0., lb = 0., lc = 0.;
+    float2 w = make_float2(0.f, 0.f);
+    __device__ GateLane(const float4* __restrict__ lines, const float2* __restrict__ uv, int q) {
+        if constexpr (TRANS) {
+            w = uv[q];
+        } else {
+            const float4 l = lines[q];
+            la = (double)l.x, lb = (double)l.y, lc = (double)l.z;
+        }
+    }
+    __device__ bool pass(const float4* __restrict__ lines, const float2* __restrict__ uv, int j, double tau) const {
+        if constexpr (TRANS) {
+            const float4 l = lines[j];
+            return gate_pass((double)l.x, (double)l.y, (double)l.z, w, tau);
+        } else {
+            return gate_pass(la, lb, lc, uv[j], tau);
+        }
+    }
+};
+
 // knn2_f32_generic_kernel's scheme (FLANN's groups of four, strictly smaller replaces), any dim
+template <bool TRANS>
 __global__ __launch_bounds__(256) void knn2_f32_gated_kernel(const float* __restrict__ A, int nA,
                                                              const float* __restrict__ B, int nB, int dim,
                                                              int rowsPerPart, const float4* __restrict__ lines,
@@ -1155,13 +1260,12 @@ __global__ __launch_bounds__(256) void knn2_f32_gated_kernel(const float* __rest
     if (q >= nA) return;
     const int jBeg = blockIdx.y * rowsPerPart;
     const int jEnd = min(nB, jBeg + rowsPerPart);
-    const float4 l = lines[q];
-    const double la = (double)l.x, lb = (double)l.y, lc = (double)l.z;
+    const GateLane<TRANS> gl(lines, uv, q);
     const float* a = A + (size_t)q * dim;
     float b1 = __builtin_inff(), b2 = __builtin_inff();
     int i1 = -1, i2 = -1;
     for (int j = jBeg; j < jEnd; j++) {
-        if (!gate_pass(la, lb, lc, uv[j], tau)) continue;
+        if (!gl.pass(lines, uv, j, tau)) continue;
         top2_insert_f(flann_l2(a, B + (size_t)j * dim, dim), j, b1, i1, b2, i2);
     }
     const size_t o = ((size_t)blockIdx.y * nA + q) * 2;
@@ -1172,7 +1276,7 @@ __global__ __launch_bounds__(256) void knn2_f32_gated_kernel(const float* __rest
 }
 
 // the popcount scan (binary rows that do not take the MFMA kernel: 16 and 64 bytes)
-template <int NW>
+template <int NW, bool TRANS>
 __global__ __launch_bounds__(256) void knn2_bits_gated_kernel(const uint32_t* __restrict__ A, int nA,
                                                               const uint32_t* __restrict__ B, int nB,
                                                               int rowsPerPart, const float4* __restrict__ lines,
@@ -1182,14 +1286,13 @@ __global__ __launch_bounds__(256) void knn2_bits_gated_kernel(const uint32_t* __
     if (q >= nA) return;
     const int jBeg = blockIdx.y * rowsPerPart;
     const int jEnd = min(nB, jBeg + rowsPerPart);
-    const float4 l = lines[q];
-    const double la = (double)l.x, lb = (double)l.y, lc = (double)l.z;
+    const GateLane<TRANS> gl(lines, uv, q);
     uint32_t a[NW];
 #pragma unroll
     for (int w = 0; w < NW; w++) a[w] = A[(size_t)q * NW + w];
     int b1 = INT_MAX, b2 = INT_MAX, i1 = -1, i2 = -1;
     for (int j = jBeg; j < jEnd; j++) {
-        if (!gate_pass(la, lb, lc, uv[j], tau)) continue;
+        if (!gl.pass(lines, uv, j, tau)) continue;
         const uint32_t* r = B + (size_t)j * NW;
         int h = 0;
 #pragma unroll
@@ -1274,7 +1377,9 @@ void launch_knn2_i8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimP
                     bool deferMerge, const EpiGate* gate) {
     if (nA <= 0) return;
     const int TRv = knn2_i8_tile_rows(dimPad, bits);
-    size_t lds = 2 * (size_t)TRv * dimPad + 2 * TRv * sizeof(int) + (gate ? 2 * TRv * sizeof(float2) : 0);
+    const bool tile = gate && gate->transposed;  // lines on the tile (float4) instead of (u, v) (float2)
+    size_t lds = 2 * (size_t)TRv * dimPad + 2 * TRv * sizeof(int) +
+                 (gate ? 2 * TRv * (tile ? sizeof(float4) : sizeof(float2)) : 0);
     const int nTiles = (nB + TRv - 1) / TRv;
     const int tilesPerPart = parts > 1 ? (nTiles + parts - 1) / parts : (nTiles > 0 ? nTiles : 1);
     int* oi = parts > 1 ? partIdx : idx;
@@ -1283,26 +1388,42 @@ void launch_knn2_i8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimP
         if (lds > 65536)
             (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         const dim3 g((nA + kQ * qg - 1) / (kQ * qg), parts);
-        kernel<<<g, kThreads, lds, s>>>(A, nA, B, nB, dimPad, cqA, ctB, tilesPerPart, oi, ok, GateArgs<false>{});
+        kernel<<<g, kThreads, lds, s>>>(A, nA, B, nB, dimPad, cqA, ctB, tilesPerPart, oi, ok, GateArgs<kGateNone>{});
     };
     auto goGated = [&](auto kernel, int qg) {
         if (lds > 65536)
             (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         const dim3 g((nA + kQ * qg - 1) / (kQ * qg), parts);
         kernel<<<g, kThreads, lds, s>>>(A, nA, B, nB, dimPad, cqA, ctB, tilesPerPart, oi, ok,
-                                        GateArgs<true>{gate->lines, gate->uv, gate->tau});
+                                        GateArgs<kGateLane>{gate->lines, gate->uv, gate->tau});
     };
-    if (gate) {
+    auto goTile = [&](auto kernel, int qg) {
+        if (lds > 65536)
+            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const dim3 g((nA + kQ * qg - 1) / (kQ * qg), parts);
+        kernel<<<g, kThreads, lds, s>>>(A, nA, B, nB, dimPad, cqA, ctB, tilesPerPart, oi, ok,
+                                        GateArgs<kGateTile>{gate->lines, gate->uv, gate->tau});
+    };
+    if (tile) {
+        if (bits)
+            goTile(knn2_i8_kernel<8, true, 1, kT, kGateTile>, 1);
+        else if (dimPad == 128)
+            goTile(knn2_i8_kernel<4, false, kQG128, kTR128, kGateTile>, kQG128);
+        else if (dimPad == 256)
+            goTile(knn2_i8_kernel<8, false, 1, kT, kGateTile>, 1);
+        else
+            goTile(knn2_i8_kernel<0, false, 1, kT, kGateTile>, 1);
+    } else if (gate) {
         // the same tile rows and queries per block as the ungated forms (knn2_i8_tile_rows,
         // knn2_i8_queries_per_block: the row constants' packing and the part count depend on them)
         if (bits)
-            goGated(knn2_i8_kernel<8, true, 1, kT, true>, 1);
+            goGated(knn2_i8_kernel<8, true, 1, kT, kGateLane>, 1);
         else if (dimPad == 128)
-            goGated(knn2_i8_kernel<4, false, kQG128, kTR128, true>, kQG128);
+            goGated(knn2_i8_kernel<4, false, kQG128, kTR128, kGateLane>, kQG128);
         else if (dimPad == 256)
-            goGated(knn2_i8_kernel<8, false, 1, kT, true>, 1);
+            goGated(knn2_i8_kernel<8, false, 1, kT, kGateLane>, 1);
         else
-            goGated(knn2_i8_kernel<0, false, 1, kT, true>, 1);
+            goGated(knn2_i8_kernel<0, false, 1, kT, kGateLane>, 1);
     } else if (bits)
         go(knn2_i8_kernel<8, true, 1>, 1);  // 32-byte binary rows unpacked to 256 int8
     else if (dimPad == 128)
@@ -1505,8 +1626,12 @@ void launch_knn2_f32_gated(const float* A, int nA, const float* B, int nB, int d
     const int grid = (nA + 255) / 256;
     const int rowsPerPart = parts > 1 ? (nB + parts - 1) / parts : (nB > 0 ? nB : 1);
     const dim3 g(grid, parts);
-    knn2_f32_gated_kernel<<<g, 256, 0, s>>>(A, nA, B, nB, dim, rowsPerPart, gate.lines, gate.uv, gate.tau,
-                                            parts > 1 ? partIdx : idx, parts > 1 ? partKey : key);
+    if (gate.transposed)
+        knn2_f32_gated_kernel<true><<<g, 256, 0, s>>>(A, nA, B, nB, dim, rowsPerPart, gate.lines, gate.uv, gate.tau,
+                                                      parts > 1 ? partIdx : idx, parts > 1 ? partKey : key);
+    else
+        knn2_f32_gated_kernel<false><<<g, 256, 0, s>>>(A, nA, B, nB, dim, rowsPerPart, gate.lines, gate.uv, gate.tau,
+                                                       parts > 1 ? partIdx : idx, parts > 1 ? partKey : key);
     if (parts > 1) knn2_f32_merge<<<grid, 256, 0, s>>>(partIdx, partKey, nA, parts, idx, key);
 }
 
@@ -1524,11 +1649,18 @@ void launch_knn2_bits(const uint8_t* A, int nA, const uint8_t* B, int nB, int di
         const float4* gl = gate->lines;
         const float2* gu = gate->uv;
         const double tau = gate->tau;
-        switch (dimBytes / 4) {
-            case 8: knn2_bits_gated_kernel<8><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
-            case 4: knn2_bits_gated_kernel<4><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
-            default: knn2_bits_gated_kernel<16><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
-        }
+        auto scan = [&](auto tr) {
+            constexpr bool T = decltype(tr)::value;
+            switch (dimBytes / 4) {
+                case 8: knn2_bits_gated_kernel<8, T><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
+                case 4: knn2_bits_gated_kernel<4, T><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
+                default: knn2_bits_gated_kernel<16, T><<<g, 256, 0, s>>>(a, nA, b, nB, rowsPerPart, gl, gu, tau, oi, ok); break;
+            }
+        };
+        if (gate->transposed)
+            scan(std::true_type());
+        else
+            scan(std::false_type());
         if (parts > 1) knn2_int_merge<<<grid, 256, 0, s>>>(partIdx, partKey, nA, parts, idx, key);
         return;
     }
@@ -1545,8 +1677,17 @@ int nndr_compact_blocks(int nA) { return nA > 0 ? (nA + 255) / 256 : 1; }
 void launch_nndr_compact(int type, const int* idx, const int* key, const float* fkey, const int* partIdx,
                          const int* partKey, int parts, int nA, double eps, int queryOffset, fm3d_dmatch* out,
                          int* count, const LookBack& lb, hipStream_t s) {
-    nndr_compact_kernel<<<nndr_compact_blocks(nA), 256, 0, s>>>(type, idx, key, fkey, partIdx, partKey, parts, nA, eps,
-                                                              queryOffset, out, count, lb);
+    nndr_compact_kernel<false><<<nndr_compact_blocks(nA), 256, 0, s>>>(type, idx, key, fkey, partIdx, partKey, parts, nA,
+                                                                     eps, queryOffset, out, count, lb, MutualArgs<false>{});
+}
+
+void launch_nndr_mutual_compact(int type, const int* idx, const int* key, const float* fkey, const int* partIdx,
+                                const int* partKey, int parts, int nA, double eps, int queryOffset,
+                                const MutualCheck& mc, fm3d_dmatch* out, int* count, const LookBack& lb,
+                                hipStream_t s) {
+    nndr_compact_kernel<true><<<nndr_compact_blocks(nA), 256, 0, s>>>(
+        type, idx, key, fkey, partIdx, partKey, parts, nA, eps, queryOffset, out, count, lb,
+        MutualArgs<true>{mc.rIdx, mc.rKey, mc.rFkey, mc.mode});
 }
 
 void launch_nndr(int type, const int* idx, const int* key, const float* fkey, int nA, int nB, double eps,

@@ -439,6 +439,13 @@ int fm3d_mgpu_create(const fm3d_settings* s, int ndev, const int* devices, int s
     create_error().clear();
     if (!s || !out || ndev <= 0 || ndev > 16 || shares < ndev || block < 0) return FM3D_ERR_INVALID;
     *out = nullptr;
+    if (s->crossCheck < 0 || s->crossCheck > 2) return FM3D_ERR_INVALID;
+    if (s->crossCheck != 0 && ndev > 1) {
+        // a device's context holds only its own queries, so its reverse search would miss the others'
+        // (one device, with any share count, holds every query in order); before any device work
+        create_error() = "Fm3d.crossCheck needs every query on one device: ndev must be 1";
+        return FM3D_ERR_UNSUPPORTED;
+    }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess) count = 0;
     const char* aliasEnv = getenv("FM3D_DEBUG_MGPU_ALIAS");

@@ -173,6 +173,7 @@ extern "C" int fm3d_settings_default(fm3d_settings* s) {
     s->lmReduction = 0;  // pixel-order sums (the reference's)
     s->dltSolver = 0;    // OpenCV 2.4 cvSVD (the reference's)
     s->guidedMatchPx = 0;  // epipolar gate off (the reference matches over the whole of frame 2)
+    s->crossCheck = 0;     // one-way matches (the reference's compareWithNNDR)
     return FM3D_OK;
 }
 
@@ -296,6 +297,7 @@ extern "C" int fm3d_settings_load(const char* path, fm3d_settings* s) {
     get_i(kv, "Fm3d.lmReduction", &s->lmReduction);
     get_i(kv, "Fm3d.dltSolver", &s->dltSolver);
     get_d(kv, "Fm3d.guidedMatchPx", &s->guidedMatchPx);
+    get_i(kv, "Fm3d.crossCheck", &s->crossCheck);
     return FM3D_OK;
 }
 

@@ -132,6 +132,13 @@ typedef struct fm3d_settings {
        0 = off, the default and the parity contract.  fm3d_ctx_create rejects negative and
        non-finite values. */
     double guidedMatchPx;
+    /* Cross-check of the match stage (not a reference key; Fm3d.crossCheck in the settings file):
+       0 = off, the default and the parity contract; 1 = keep a match (i, j) only when query i is also
+       the nearest query of train row j (mutual nearest neighbours, OpenCV's BFMatcher crossCheck, on
+       top of the NNDR rule); 2 = 1 and row j's two nearest queries pass the NNDR rule as well
+       (fm3d_match_mutual).  Combines with guidedMatchPx.  fm3d_ctx_create rejects
+       other values; fm3d_mgpu_create rejects a non-zero value on more than one device. */
+    int crossCheck;
 } fm3d_settings;
 
 #define FM3D_FEAT_SURF 0
@@ -256,6 +263,23 @@ int fm3d_knn2_guided(fm3d_ctx *ctx, const void *descA, int nA, const void *descB
 int fm3d_match_nndr_guided(fm3d_ctx *ctx, const void *descA, int nA, const void *descB, int nB, int dim, int type,
                            const fm3d_point2f *kpts1, const fm3d_point2f *kpts2, double epsilon, double maxPx,
                            fm3d_dmatch *matches, int *nMatches);
+
+/* Cross-checked forms of fm3d_match_nndr and fm3d_match_nndr_guided.  With fwd =
+   fm3d_knn2(A, B) and rev = fm3d_knn2(B, A) (for every train row its two nearest queries, order
+   (distance, queryIdx), lowest index first on ties), query i's best match (i, j) is kept iff
+     - the NNDR rule of fm3d_match_nndr holds for fwd[i], and
+     - rev[j][0].queryIdx == i, and
+     - mode 2 only: rev[j] has two neighbours and rev[j][0].distance <= epsilon * rev[j][1].distance.
+   mode: 1 (mutual nearest) or 2 (symmetric ratio).  The guided form ranks, in both searches, the
+   pairs (i, j) that pass fm3d_knn2_guided's gate (the line of query i, the point of train row j: one
+   predicate, not a second gate from image-1 epipolar lines).  Output as fm3d_match_nndr: query order,
+   the forward distance; nA == 0 or nB == 0 gives 0 matches.
+   FM3D_ERR_INVALID: a null pointer, a mode outside {1, 2}; guided: g12 not set, a bad maxPx. */
+int fm3d_match_mutual(fm3d_ctx *ctx, const void *descA, int nA, const void *descB, int nB, int dim, int type,
+                      double epsilon, int mode, fm3d_dmatch *matches, int *nMatches);
+int fm3d_match_mutual_guided(fm3d_ctx *ctx, const void *descA, int nA, const void *descB, int nB, int dim, int type,
+                             const fm3d_point2f *kpts1, const fm3d_point2f *kpts2, double epsilon, double maxPx,
+                             int mode, fm3d_dmatch *matches, int *nMatches);
 
 /* ---------------- SingleCameraTriangulator ---------------- */
 /* setg12 (singlecameratriangulator.cpp:123-143): g12 = gIC^-1 g2^-1 g1 gIC, row-major 4x4 */

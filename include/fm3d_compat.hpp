@@ -188,6 +188,23 @@ public:
     inline void compareWithNNDRGuided(double epsilon, double maxPx, const SingleCameraTriangulator& triangulator,
                                       std::vector<DMatch>& matches, const std::vector<KeyPoint>& kpts_a,
                                       const std::vector<KeyPoint>& kpts_b, const DescMat& A, const DescMat& B);
+    // compareWithNNDR with the cross-check (fm3d_match_mutual; OpenCV's BFMatcher crossCheck on top of
+    // the ratio test): mode 1 keeps a match only when the query is also its train row's nearest query,
+    // mode 2 asks the train row's two nearest queries to pass the ratio test as well
+    void compareWithNNDRMutual(double epsilon, std::vector<DMatch>& matches, const DescMat& A, const DescMat& B,
+                               int mode = 1) {
+        require_same(A, B);
+        std::vector<DMatch> tmp(A.rows > 0 ? A.rows : 1);
+        int n = 0;
+        check(d_.ctx(), fm3d_match_mutual(d_.ctx(), A.data, A.rows, B.data, B.rows, A.cols, A.type, epsilon, mode,
+                                          tmp.data(), &n));
+        matches.insert(matches.end(), tmp.begin(), tmp.begin() + n);
+    }
+    // the cross-check over the pairs inside compareWithNNDRGuided's gate (fm3d_match_mutual_guided)
+    inline void compareWithNNDRMutualGuided(double epsilon, double maxPx, const SingleCameraTriangulator& triangulator,
+                                            std::vector<DMatch>& matches, const std::vector<KeyPoint>& kpts_a,
+                                            const std::vector<KeyPoint>& kpts_b, const DescMat& A, const DescMat& B,
+                                            int mode = 1);
 
 private:
     static void require_same(const DescMat& A, const DescMat& B) {
@@ -277,6 +294,26 @@ inline void DescriptorsMatcher::compareWithNNDRGuided(double epsilon, double max
     int n = 0;
     check(d_.ctx(), fm3d_match_nndr_guided(d_.ctx(), A.data, A.rows, B.data, B.rows, A.cols, A.type, k1.data(),
                                            k2.data(), epsilon, maxPx, tmp.data(), &n));
+    matches.insert(matches.end(), tmp.begin(), tmp.begin() + n);
+}
+
+inline void DescriptorsMatcher::compareWithNNDRMutualGuided(double epsilon, double maxPx,
+                                                            const SingleCameraTriangulator& triangulator,
+                                                            std::vector<DMatch>& matches,
+                                                            const std::vector<KeyPoint>& kpts_a,
+                                                            const std::vector<KeyPoint>& kpts_b, const DescMat& A,
+                                                            const DescMat& B, int mode) {
+    require_same(A, B);
+    if (&triangulator.device() != &d_) throw Error(FM3D_ERR_INVALID, "the triangulator's pose lives on another device");
+    if ((int)kpts_a.size() != A.rows || (int)kpts_b.size() != B.rows)
+        throw Error(FM3D_ERR_INVALID, "one keypoint per descriptor row");
+    std::vector<fm3d_point2f> k1(kpts_a.size()), k2(kpts_b.size());
+    for (size_t i = 0; i < kpts_a.size(); i++) k1[i] = fm3d_point2f{kpts_a[i].pt.x, kpts_a[i].pt.y};
+    for (size_t i = 0; i < kpts_b.size(); i++) k2[i] = fm3d_point2f{kpts_b[i].pt.x, kpts_b[i].pt.y};
+    std::vector<DMatch> tmp(A.rows > 0 ? A.rows : 1);
+    int n = 0;
+    check(d_.ctx(), fm3d_match_mutual_guided(d_.ctx(), A.data, A.rows, B.data, B.rows, A.cols, A.type, k1.data(),
+                                             k2.data(), epsilon, maxPx, mode, tmp.data(), &n));
     matches.insert(matches.end(), tmp.begin(), tmp.begin() + n);
 }
 
