@@ -851,13 +851,40 @@ __global__ __launch_bounds__(256) void nndr_compact_kernel(int type, const int* 
 // ---------------- float rows: a bf16 MFMA prefilter, then the exact FLANN-order distances ----------------
 // s'_j = |b_j|^2 - 2 a_hi . b_hi,j (a_hi, b_hi = the rows rounded to bf16; the dot products on
 // v_mfma_f32_32x32x16_bf16, |b_j|^2 in fp32) ranks train row j for query a up to
-//   |s'_j - s_j| <= eps_q = 0.0079 |a| Bmax + 1e-5 Bmax^2        (s_j = |a - b_j|^2 - |a|^2)
-// (bf16 rounding 2^-9 per element, an exact bf16 product and <= 127 fp32 roundings per dot, the
-// fp32 norm), and FLANN's float L2 is within phi_q = 2e-5 (|a| + Bmax)^2 of the true distance
-// (dim <= 128).  So every member of the exact top-2 has s'_j <= s'_(2) + 2 eps_q + 2 phi_q: pass 1
-// finds s'_(2), pass 2 lists the rows under that bound, pass 3 computes their exact FLANN-order
-// distances and keeps the (distance, index) top-2 -- the same two rows and keys the full exact scan
-// returns.  A query with more than kCandMax such rows, or a non-finite norm, is rescanned exactly.
+//   |s'_j - s_j| <= eps_q = kBf16KeyCoef |a| Bmax + kNormCoef Bmax^2   (s_j = |a - b_j|^2 - |a|^2)
+// and FLANN's float L2 is within phi_q = kFlannCoef (|a| + Bmax)^2 of the true distance (the
+// derivations stand at the constants below).  A member j of the exact top-2 is no farther, in
+// FLANN's floats, than one of the two rows k that hold s'_(1) and s'_(2), so s_j <= s_k + 2 phi_q and
+// s'_j <= s'_k + 2 eps_q + 2 phi_q <= s'_(2) + 2 eps_q + 2 phi_q: pass 1 finds s'_(2), pass 2 lists
+// the rows under that bound, pass 3 computes their exact FLANN-order distances and keeps the
+// (distance, index) top-2 -- the same two rows and keys the full exact scan returns.  A query with
+// more than kCandMax such rows, or a non-finite norm, is rescanned exactly.
+// (tests/test_f32_prefilter_bound.py pins the model on the CPU, with rows whose rounding errors all
+// push one way; tests/test_gpu_f32_mfma.py runs them and every route through the library)
+//
+// kBf16KeyCoef: bf16 keeps 8 significand bits, so rounding to nearest moves an element by at most
+// u = 2^-8 relative (not 2^-9: that is the spacing's half at the top of a binade only).  The bf16
+// products are exact in fp32, a_hi b_hi = a b (1 + d)(1 + d'), off by at most (2u + u^2)|a b|;
+// summed, by Cauchy-Schwarz, (2u + u^2)|a||b|, and the key carries the dot twice:
+// 2 (2u + u^2) = 0.0156555.  The dot's fp32 accumulation, <= 128 roundings of 2^-24 (the MFMA's
+// order is its own, the count is not), doubled: 2 * 128 * 2^-24 = 0.0000153; the key's final FMA
+// adds 2^-24 (2.02 |a||b|) = 0.0000001.  Sum 0.0156709, rounded up to 0.0158 -- the 0.00013 left
+// over would cover eight times the accumulation term.  Rows with all errors aligned reach 0.01559.
+// kNormCoef: |b|^2 in fp32 is dim products and dim - 1 sums of non-negative terms, (dim + 1) 2^-24
+// relative at most, and the key's final FMA rounds it once more: 130 * 2^-24 = 7.8e-6 <= 1e-5.
+// kFlannCoef: FLANN's L2 rounds a - b once (twice 2^-24 after squaring), the square, three sums in
+// the group of four and dim / 4 = 32 sums into the result: 38 roundings on terms that sum to
+// |a - b|^2 <= (|a| + Bmax)^2, 38 * 2^-24 = 2.3e-6 <= 2e-5.
+// kSlackCoef (|a| + Bmax)^2 covers the bound's own fp32 arithmetic: s'_(2) + margin rounds once,
+// 2^-24 (Bmax^2 + 2.02 |a| Bmax + margin) < 1.3e-7 (|a| + Bmax)^2 <= 1e-6 (|a| + Bmax)^2.
+constexpr double kBf16KeyCoef = 0.0158;
+constexpr double kNormCoef = 1e-5;
+constexpr double kFlannCoef = 2e-5;
+constexpr double kSlackCoef = 1e-6;
+// 2 eps_q + 2 phi_q + slack
+__device__ inline double knn2_bf16_margin(double a, double bm) {
+    return 2 * (kBf16KeyCoef * a * bm + kNormCoef * bm * bm) + (2 * kFlannCoef + kSlackCoef) * (a + bm) * (a + bm);
+}
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 constexpr int kCandMax = 32;
@@ -1051,8 +1078,7 @@ __global__ void knn2_bf16_bound_kernel(const float* __restrict__ partKey, int nA
         p1 = fminf(p1, c1);
     }
     const double a = sqrt((double)nA2[q]), bm = sqrt((double)__uint_as_float(*bmax));
-    const double eps = 0.0079 * a * bm + 1e-5 * bm * bm, phi = 2e-5 * (a + bm) * (a + bm);
-    const double t = (double)p2 + 2 * eps + 2 * phi + 1e-6 * (a + bm) * (a + bm);
+    const double t = (double)p2 + knn2_bf16_margin(a, bm);
     // (rows of norm below 1e-10 are rescanned: the bound does not cover the MFMA's denormal handling)
     const bool ok = t == t && t < 1e37 && a < 1e18 && a + bm > 1e-10;
     float t32 = (float)t;
@@ -1120,7 +1146,7 @@ __global__ void knn2_bf16_margin_kernel(const float* __restrict__ nA2, int nA, c
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nA) return;
     const double a = sqrt((double)nA2[q]), bm = sqrt((double)__uint_as_float(*bmax));
-    const double m = 2 * (0.0079 * a * bm + 1e-5 * bm * bm) + 2 * 2e-5 * (a + bm) * (a + bm) + 1e-6 * (a + bm) * (a + bm);
+    const double m = knn2_bf16_margin(a, bm);
     const bool ok = m == m && m < 1e37 && a < 1e18 && a + bm > 1e-10;
     float m32 = (float)m;
     if ((double)m32 < m) m32 = nextafterf(m32, __builtin_inff());

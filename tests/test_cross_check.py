@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import f32_prefilter_pyref as pf
 from conftest import oracle_threads
 
 pytestmark = pytest.mark.gpu
@@ -210,6 +211,20 @@ def test_float_prefilter_route(fm3d, orc, ctx, kind):
     assert 0 < len(mutual_ref(orc, fwd, rev, 1.0, 1)[0]) < len(orc.nndr(fwd[0], fwd[1], 1.0)[0])
     for mode, eps in MODES_EPS:
         assert_matches(dm.compareWithNNDRMutual(eps, a, b, mode=mode), mutual_ref(orc, fwd, rev, eps, mode))
+
+
+def test_float_prefilter_correlated_rounding(fm3d, orc, ctx):
+    """the mutual check consumes the forward search's first neighbour.  Rows whose bf16 rounding errors
+    all push one way (tests/f32_prefilter_pyref.py): each such query's nearest row is b*, whose own
+    nearest query is a short ordinary one, so the pair is dropped -- while the decoy that a too
+    tight prefilter bound returns instead has that query as its nearest, and the pair would be kept"""
+    a, b, queries, rows = pf.correlated_rounding_case(128, 2048, 2051, 12, seed=128)
+    fwd, rev = two_way(orc, a, b, orc.F32)
+    ref = mutual_ref(orc, fwd, rev, 1.0, 1)
+    assert len(ref[0]) > 1000 and not np.isin(queries, ref[0]).any()
+    assert (rev[0][rows[:, 1], 0] == queries).sum() >= 10
+    out = fm3d.DescriptorsMatcher(ctx).compareWithNNDRMutual(1.0, a, b, mode=1)
+    assert_matches(out, ref)
 
 
 # ---------------------------------------------------------------- 2. ties

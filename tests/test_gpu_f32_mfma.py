@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import f32_prefilter_pyref as pf
 from conftest import oracle_threads
 
 pytestmark = pytest.mark.gpu
@@ -98,3 +99,65 @@ def test_f32_mfma_nonfinite_rows_rescanned(fm3d, orc, ctx):
     got = dm.knn_match(A, B)
     assert got.tobytes() == _knn(dm, A, B, FM3D_F32_FUSED="0").tobytes()
     assert got.tobytes() == _knn(dm, A, B, FM3D_F32_MFMA="0").tobytes()
+
+
+# ---------------------------------------------------------------- the bound's error model and the routes
+# (inputs and their expected list lengths: tests/f32_prefilter_pyref.py, tests/test_f32_prefilter_bound.py)
+NA, NB = 2048, 2051  # the smallest calls that take the prefilter: 2^22 pairs, a partial last tile, 4 train parts
+
+
+@pytest.mark.parametrize("dim", [128, 64])
+def test_f32_mfma_correlated_bf16_rounding(fm3d, orc, ctx, dim):
+    """triples whose bf16 rounding errors all push the same way: |s' - s| reaches 0.00996 |a| B_max, and
+    a bound built on 2^-9 per element (0.0079 |a| B_max) drops the exact nearest row b* (with that
+    coefficient the library returned the two decoys, e.g. rows [2049, 2050] for query 0 where the exact
+    scan returns [0, 2049]: 11 of the 12 queries at dim 128, all 12 at dim 64)"""
+    A, B, queries, rows = pf.correlated_rounding_case(dim, NA, NB, 12, seed=dim)
+    dm = fm3d.DescriptorsMatcher(ctx)
+    for env in ({}, {"FM3D_F32_FUSED": "0"}):
+        got = _knn(dm, A, B, **env)["trainIdx"][queries]
+        print("dim", dim, env, "query", int(queries[0]), "got", got[0].tolist(), "want", rows[0, :2].tolist(),
+              "| queries off:", queries[(got != rows[:, :2]).any(axis=1)].tolist())
+        assert np.array_equal(got, rows[:, :2])
+    _check(fm3d, orc, ctx, A, B)
+
+
+def test_f32_mfma_retry_route(fm3d, orc, ctx):
+    """|b_j|^2 strictly decreasing, a quarter of the queries tiny: their fused lists overflow (every
+    row a running best), the two-pass retry lists two rows for each"""
+    A, B, nTiny = pf.retry_route_case(128, NA, NB, seed=21)
+    _check(fm3d, orc, ctx, A, B)
+    got = fm3d.DescriptorsMatcher(ctx).knn_match(A, B)
+    assert np.all(got["trainIdx"][:nTiny] >= 0)
+
+
+def _duplicates(fm3d, orc, ctx, share):
+    A, B, dupq, top2 = pf.duplicates_case(128, NA, NB, share, seed=share)
+    _check(fm3d, orc, ctx, A, B)
+    got = fm3d.DescriptorsMatcher(ctx).knn_match(A, B)
+    assert np.array_equal(got["trainIdx"][dupq], top2)
+
+
+def test_f32_mfma_rescan_route(fm3d, orc, ctx):
+    """140 copies of the nearest row of 1/16 of the queries, over all tiles and parts: the fused pass
+    keeps its lists and the rescan kernel serves those queries (lowest two copies, equal distances)"""
+    _duplicates(fm3d, orc, ctx, 16)
+
+
+def test_f32_mfma_valu_fallback_route(fm3d, orc, ctx):
+    """the same for 1/4 of the queries: both forms break the 1/8 rule and the call ends on the VALU scan"""
+    _duplicates(fm3d, orc, ctx, 4)
+
+
+@pytest.fixture(scope="module")
+def magnitudes():
+    return pf.magnitude_cases(128, NA, NB, seed=31)
+
+
+@pytest.mark.parametrize("case", ["tiny", "large", "huge_query", "outlier_row", "bf16_inf"])
+def test_f32_mfma_magnitudes(fm3d, orc, ctx, magnitudes, case):
+    """the problem scaled by 1e-12 (norms under the 1e-10 rescan threshold) and by 1e15, queries of norm
+    2e18 and 2e19 (|a| >= 1e18; the larger one's fp32 norm overflows), a train row of norm 1e6 among
+    unit rows (the margin swallows every row), a finite fp32 element that is +inf in bf16"""
+    A, B = magnitudes[case]
+    _check(fm3d, orc, ctx, A, B)
