@@ -46,8 +46,19 @@ EXPORTS = (
     "fm3d_mser_detect", "fm3d_mser_detect_batch", "fm3d_mser_regions", "fm3d_pipeline_submit_dlt", "fm3d_pipeline_submit_dlt_pair",
     "fm3d_pipeline_submit_ncc", "fm3d_pipeline_wait_ncc", "fm3d_pipeline_wait_dlt", "fm3d_device_count",
     "fm3d_epipolar_matrix", "fm3d_epipolar_lines", "fm3d_knn2_guided", "fm3d_match_nndr_guided",
-    "fm3d_match_mutual", "fm3d_match_mutual_guided",
+    "fm3d_match_mutual", "fm3d_match_mutual_guided", "fm3d_math_probe",
 )
+
+# include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
+PROBE_FNS = (
+    "sin_cr", "cos_cr", "sincos_sel_cr0", "sincos_sel_cr1", "atan2_cr", "exp_cr", "hypot_cr",
+    "sin", "cos", "atan2", "acos", "exp",
+    "mdiv", "mdiv_fast", "recip_z", "recip_z_lo", "div_nn",
+    "div_f64", "sqrt_f64", "div_f32", "sqrt_f32",
+    "cv_exp_sse", "cv_exp_scalar", "cv_atan2_deg", "cv_exp2f", "cv_roundf", "cv_round", "cv_floorf",
+)
+PROBE_BINARY = frozenset(("atan2_cr", "hypot_cr", "atan2", "mdiv", "mdiv_fast", "div_nn", "div_f64", "div_f32",
+                          "cv_atan2_deg"))
 
 
 class Fm3dError(RuntimeError):
@@ -1099,6 +1110,27 @@ class Pipeline:
 
 
 SHARE_BLOCK = 4096  # queries per block of the block-cyclic partition (fm3d_mgpu, shard.py)
+
+
+def math_probe(ctx: "Context", fn_name: str, x, y=None) -> np.ndarray:
+    """fm3d_math_probe: function fn_name (PROBE_FNS) of the shared math headers on the device,
+    elementwise over x (and y for PROBE_BINARY; the first array is the first argument).  Float
+    functions take and return floats widened exactly to double."""
+    if fn_name not in PROBE_FNS:
+        raise Fm3dError(ERR_INVALID, f"unknown probe function {fn_name!r}")
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    if fn_name in PROBE_BINARY:
+        if y is None:
+            raise Fm3dError(ERR_INVALID, f"{fn_name} takes two arguments")
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        if y.size != x.size:
+            raise Fm3dError(ERR_INVALID, "x and y differ in length")
+    else:
+        y = None
+    out = np.empty_like(x)
+    ctx.check(lib().fm3d_math_probe(ctx.handle, ctypes.c_int(PROBE_FNS.index(fn_name)), _ptr(x),
+                                    _ptr(y) if y is not None else None, ctypes.c_int(x.size), _ptr(out)))
+    return out
 
 
 def device_count() -> int:

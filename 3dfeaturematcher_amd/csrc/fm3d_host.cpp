@@ -4447,4 +4447,27 @@ int fm3d_undistort(fm3d_ctx* c, const double* xy, int n, double* out) {
     return FM3D_OK;
 }
 
+int fm3d_math_probe(fm3d_ctx* c, int fn, const double* x, const double* y, int n, double* out) {
+    if (!c || n < 0 || fn < 0 || fn >= FM3D_PROBE_COUNT || !x || !out) return FM3D_ERR_INVALID;
+    const bool binary = fm3d::math_probe_binary(fn);
+    if (binary && !y) return FM3D_ERR_INVALID;
+    if (n == 0) return FM3D_OK;
+    hipSetDevice(c->device);
+    const size_t bytes = (size_t)n * sizeof(double);
+    DevBuf a, b, o;
+    HIPCHK(c, a.ensure(bytes));
+    if (binary) HIPCHK(c, b.ensure(bytes));
+    HIPCHK(c, o.ensure(bytes));
+    HIPCHK(c, hipMemcpy(a.p, x, bytes, hipMemcpyHostToDevice));
+    if (binary) HIPCHK(c, hipMemcpy(b.p, y, bytes, hipMemcpyHostToDevice));
+    fm3d::launch_math_probe(fn, a.as<double>(), binary ? b.as<double>() : nullptr, n, o.as<double>(), c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, o.p, bytes, hipMemcpyDeviceToHost));
+    a.release();
+    b.release();
+    o.release();
+    return FM3D_OK;
+}
+
 }  // extern "C"

@@ -409,6 +409,11 @@ int triangulate_compact_blocks(int K);
 void launch_pyrdown(const uint8_t* src, int w, int h, uint8_t* dst, hipStream_t s);
 void launch_undistort(const Camera& cam, const double* xy, int n, double* out, hipStream_t s);
 
+// ---------------- the shared math headers, element-wise (fm3d_probe.hip) ----------------
+// out[i] = function fn (FM3D_PROBE_*) of x[i] and, where math_probe_binary(fn), y[i]
+bool math_probe_binary(int fn);
+void launch_math_probe(int fn, const double* x, const double* y, int n, double* out, hipStream_t s);
+
 // extractPixelsContour + the level-0 geometry of evaluateNormal through a given plane (fm3d_misc.hip)
 struct PlaneProjParams {
     Camera cam;

@@ -649,6 +649,51 @@ int fm3d_plane_to_image2(fm3d_ctx *ctx, const double X[3], const double n[3], do
 /* cv::undistortPoints of n pixel coordinates (device kernel) */
 int fm3d_undistort(fm3d_ctx *ctx, const double *xy, int n, double *out);
 
+/* The shared math headers on the device, one element per thread (test entry): out[i] =
+   function fn of x[i] (and y[i] where it takes two arguments; y may be NULL otherwise), compiled
+   into the library with the flags of every other kernel.  The float functions take and return
+   their values widened exactly to double, the integer-valued ones return the integer as a double.
+   The Python wrapper mirrors this table by position. */
+enum {
+    /* fm3d_crmath.h */
+    FM3D_PROBE_SIN_CR = 0,
+    FM3D_PROBE_COS_CR,
+    FM3D_PROBE_SINCOS_SEL_CR0, /* the LM kernel's form, cosine 0 */
+    FM3D_PROBE_SINCOS_SEL_CR1, /* cosine 1 */
+    FM3D_PROBE_ATAN2_CR,       /* (y, x) = (x[i], y[i]): the first array is the first argument */
+    FM3D_PROBE_EXP_CR,
+    FM3D_PROBE_HYPOT_CR,
+    /* fm3d_detmath.h */
+    FM3D_PROBE_SIN,
+    FM3D_PROBE_COS,
+    FM3D_PROBE_ATAN2,
+    FM3D_PROBE_ACOS,
+    FM3D_PROBE_EXP,
+    /* csrc/fm3d_fastdiv.h; the reciprocal 1.0 / d and the pass guards computed per lane */
+    FM3D_PROBE_MDIV,       /* (a, d), guarded */
+    FM3D_PROBE_MDIV_FAST,  /* (a, d), the caller keeps the guard */
+    FM3D_PROBE_RECIP_Z,
+    FM3D_PROBE_RECIP_Z_LO,
+    FM3D_PROBE_DIV_NN,     /* (mm, nn) */
+    /* the plain operators (they pin the build flags) */
+    FM3D_PROBE_DIV_F64,
+    FM3D_PROBE_SQRT_F64,
+    FM3D_PROBE_DIV_F32,
+    FM3D_PROBE_SQRT_F32,
+    /* fm3d_cvmath.h */
+    FM3D_PROBE_CV_EXP_SSE,
+    FM3D_PROBE_CV_EXP_SCALAR,
+    FM3D_PROBE_CV_ATAN2_DEG, /* (y, x) */
+    FM3D_PROBE_CV_EXP2F,
+    FM3D_PROBE_CV_ROUNDF,
+    FM3D_PROBE_CV_ROUND,
+    FM3D_PROBE_CV_FLOORF,
+    FM3D_PROBE_COUNT
+};
+/* FM3D_ERR_INVALID: a null ctx, x or out (or y for a function of two arguments), n < 0, fn outside
+   [0, FM3D_PROBE_COUNT).  n == 0 returns at once. */
+int fm3d_math_probe(fm3d_ctx *ctx, int fn, const double *x, const double *y, int n, double *out);
+
 /* library version string */
 const char *fm3d_version(void);
 

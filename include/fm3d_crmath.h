@@ -211,10 +211,9 @@ FM3D_HD fm3d_dd fm3d_cr_atan01(fm3d_dd t)
         {-0.14285714285714285, 0}, {0.1111111111111111, 0}, {-0.09090909090909091, 0},
         {0.07692307692307693, 0}, {-0.06666666666666667, 0}, {0.058823529411764705, 0},
         {-0.05263157894736842, 0}};
-    double c, p;
-    int j = (int)floor(t.hi * 16.0 + 0.5), n;
+    double c, p, jf = floor(t.hi * 16.0 + 0.5);
+    int j = jf < 16.0 ? (jf > 0.0 ? (int)jf : 0) : 16, n; /* a NaN t takes 16 and stays NaN: no wild index */
     fm3d_dd u, u2, P;
-    if (j > 16) j = 16;
     c = (double)j * 0.0625;
     u = j ? fm3d_dd_div(fm3d_dd_add_d(t, -c), fm3d_dd_add_d(fm3d_dd_mul_d(t, c), 1.0)) : t;
     u2 = fm3d_dd_mul(u, u);
@@ -225,21 +224,44 @@ FM3D_HD fm3d_dd fm3d_cr_atan01(fm3d_dd t)
     return fm3d_dd_add(fm3d_dd_make(A[j][0], A[j][1]), fm3d_dd_add(u, fm3d_dd_mul(fm3d_dd_mul(u, u2), P)));
 }
 
+/* Every finite, non-zero pair.  The Dekker products of fm3d_dd_div are exact only while the
+   operands and their error terms stay normal and 134217729 * a does not overflow, so a pair with
+   an operand above 2^500 or below 2^-500 is first brought into that range (every other pair, the LM's
+   among them, takes the unscaled operations):
+     - min <= 2^-60 max: atan(t) = t (1 - t^2/3 + ...) with t^2 < 2^-120 rounds as t = min / max
+       does, so t is the IEEE quotient of the unscaled operands (it may be subnormal or 0; a
+       subnormal quotient that is an exact tie rounds to even where atan(t) < t rounds down: the
+       last subnormal bit) -- returned as it is in the first octant, a term below 2^-60 of the
+       double-double pi/2 or pi elsewhere;
+     - else both operands times 2^-600 (max > 2^500) or 2^600 (min < 2^-500): exact, the ratio
+       unchanged, 2^-474 <= min and max <= 2^424. */
 FM3D_HD double fm3d_atan2_cr(double y, double x)
 {
-    double ax, ay;
-    fm3d_dd a;
+    double ax, ay, lo, hi;
+    fm3d_dd a, t;
+    int tiny = 0;
     if (x != x || y != y) return x + y;
     ax = fabs(x);
     ay = fabs(y);
     /* zeros and infinities: fm3d_detmath.h's exact special values */
     if (ay == 0.0 || ax == 0.0 || ax - ax != 0.0 || ay - ay != 0.0) return fm3d_atan2(y, x);
-    if (ay <= ax) {
-        a = fm3d_cr_atan01(fm3d_dd_div(fm3d_dd_make(ay, 0.), fm3d_dd_make(ax, 0.)));
-    } else {
-        a = fm3d_dd_sub(fm3d_dd_make(FM3D_PIO2_HI, FM3D_PIO2_LO),
-                        fm3d_cr_atan01(fm3d_dd_div(fm3d_dd_make(ax, 0.), fm3d_dd_make(ay, 0.))));
+    lo = ay <= ax ? ay : ax;
+    hi = ay <= ax ? ax : ay;
+    if (hi > 0x1p+500 || lo < 0x1p-500) {
+        if (lo <= hi * 0x1p-60) {
+            tiny = 1;
+            lo = lo / hi;
+            if (ay <= ax && x > 0.0) return y < 0.0 ? -lo : lo;
+        } else if (hi > 0x1p+500) {
+            lo *= 0x1p-600;
+            hi *= 0x1p-600;
+        } else {
+            lo *= 0x1p+600;
+            hi *= 0x1p+600;
+        }
     }
+    t = tiny ? fm3d_dd_make(lo, 0.) : fm3d_cr_atan01(fm3d_dd_div(fm3d_dd_make(lo, 0.), fm3d_dd_make(hi, 0.)));
+    a = ay <= ax ? t : fm3d_dd_sub(fm3d_dd_make(FM3D_PIO2_HI, FM3D_PIO2_LO), t);
     if (x < 0.0) a = fm3d_dd_sub(fm3d_dd_make(FM3D_PI_HI, FM3D_PI_LO), a);
     return y < 0.0 ? -fm3d_dd_round(a) : fm3d_dd_round(a);
 }

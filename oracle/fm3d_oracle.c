@@ -52,6 +52,7 @@
 #endif
 #include "fm3d_detmath.h"
 #include "fm3d_crmath.h"
+#include "fm3d_cvmath.h"
 
 #define ORC_API __attribute__((visibility("default")))
 
@@ -1011,16 +1012,39 @@ static double orc_fexp(int mode, double x)
     if (!(mode & ORC_LM_DETMATH) || (mode & ORC_LIBM_EXP)) return exp(x);
     return (mode & ORC_DET_1ULP) ? fm3d_exp(x) : fm3d_exp_cr(x);
 }
-/* the four transcendentals elementwise in a mode (tests/test_crmath.py pins the correctly rounded
-   ones against mpmath): fn 0 sin(x), 1 cos(x), 2 atan2(x, y), 3 exp(x), 4 hypot(x, y) (DETMATH:
-   fm3d_hypot_cr, the SVD's; else libm) */
+/* the shared math headers elementwise in a mode (tests/test_crmath.py pins the correctly rounded
+   functions against mpmath; tests/test_gpu_math_probe.py compares the device build of the same
+   headers with this one): fn 0 sin(x), 1 cos(x), 2 atan2(x, y), 3 exp(x), 4 hypot(x, y) (DETMATH:
+   fm3d_hypot_cr, the SVD's; else libm), 5 / 6 the LM kernel's fm3d_sincos_sel_cr(x, 0 / 1) (its
+   1-ulp and libm modes: sin / cos), 7 acos(x) (DETMATH: fm3d_acos), and fm3d_cvmath.h's float
+   functions, their arguments and results widened exactly to double, in every mode: 8
+   fm3d_cv_exp_sse, 9 fm3d_cv_exp_scalar, 10 fm3d_cv_atan2_deg(x, y), 11 fm3d_cv_exp2f, 12
+   fm3d_cv_roundf, 13 fm3d_cv_round (of the double), 14 fm3d_cv_floorf */
+static double orc_math_one(int fn, int mode, double x, double y)
+{
+    switch (fn) {
+    case 0: return orc_fsin(mode, x);
+    case 1: return orc_fcos(mode, x);
+    case 2: return orc_fatan2(mode, x, y);
+    case 3: return orc_fexp(mode, x);
+    case 4: return (mode & ORC_LM_DETMATH) ? fm3d_hypot_cr(x, y) : hypot(x, y);
+    case 5: return (mode & ORC_LM_DETMATH) && !(mode & (ORC_DET_1ULP | ORC_LIBM_SIN)) ? fm3d_sincos_sel_cr(x, 0) : orc_fsin(mode, x);
+    case 6: return (mode & ORC_LM_DETMATH) && !(mode & (ORC_DET_1ULP | ORC_LIBM_COS)) ? fm3d_sincos_sel_cr(x, 1) : orc_fcos(mode, x);
+    case 7: return (mode & ORC_LM_DETMATH) ? fm3d_acos(x) : acos(x);
+    case 8: return (double)fm3d_cv_exp_sse((float)x);
+    case 9: return (double)fm3d_cv_exp_scalar((float)x);
+    case 10: return (double)fm3d_cv_atan2_deg((float)x, (float)y);
+    case 11: return (double)fm3d_cv_exp2f((float)x);
+    case 12: return (double)fm3d_cv_roundf((float)x);
+    case 13: return (double)fm3d_cv_round(x);
+    case 14: return (double)fm3d_cv_floorf((float)x);
+    default: return NAN;
+    }
+}
 ORC_API void orc_math_eval(int fn, int mode, const double *x, const double *y, int n, double *out)
 {
     int i;
-    for (i = 0; i < n; i++)
-        out[i] = fn == 0 ? orc_fsin(mode, x[i]) : fn == 1 ? orc_fcos(mode, x[i])
-               : fn == 2 ? orc_fatan2(mode, x[i], y[i]) : fn == 3 ? orc_fexp(mode, x[i])
-               : (mode & ORC_LM_DETMATH) ? fm3d_hypot_cr(x[i], y[i]) : hypot(x[i], y[i]);
+    for (i = 0; i < n; i++) out[i] = orc_math_one(fn, mode, x[i], y[i]);
 }
 
 static void orc_sph2car(int mode, double phi, double theta, double n[3])

@@ -30,11 +30,18 @@ def tree_stats(reset=False):
             arr[i] = 0
     return out
 
+MATH_FNS = {"sin": 0, "cos": 1, "atan2": 2, "exp": 3, "hypot": 4, "sincos_sel0": 5, "sincos_sel1": 6, "acos": 7,
+            "cv_exp_sse": 8, "cv_exp_scalar": 9, "cv_atan2_deg": 10, "cv_exp2f": 11, "cv_roundf": 12,
+            "cv_round": 13, "cv_floorf": 14}
+
+
 def math_eval(fn, x, y=None, mode=DETMATH):
-    """orc_math_eval: fn "sin", "cos", "exp" of x, or "atan2" / "hypot" of (x, y), elementwise,
+    """orc_math_eval: fn "sin", "cos", "exp", "acos" of x, or "atan2" / "hypot" of (x, y), elementwise,
     in an oracle mode (DETMATH: include/fm3d_crmath.h's correctly rounded functions; DETMATH |
-    DET_1ULP: fm3d_detmath.h's; 0: libm)."""
-    f = {"sin": 0, "cos": 1, "atan2": 2, "exp": 3, "hypot": 4}[fn]
+    DET_1ULP: fm3d_detmath.h's; 0: libm); "sincos_sel0" / "sincos_sel1": the LM kernel's
+    fm3d_sincos_sel_cr(x, 0 / 1); "cv_*": include/fm3d_cvmath.h's float functions (any mode), float
+    arguments and results widened exactly to double."""
+    f = MATH_FNS[fn]
     x = np.ascontiguousarray(x, dtype=np.float64)
     y = x if y is None else np.ascontiguousarray(y, dtype=np.float64)
     out = np.empty_like(x)

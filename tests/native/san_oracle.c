@@ -101,6 +101,41 @@ int main(void)
         orc_ncc_hypotheses(&c0, R2i, t2i, i1, i2, 64, 48, nx, 3, 5, 64, 48, 2.4, 8, 4, 0.4, sc, nn, bb);
         orc_ncc_hypotheses(&c0, R2i, t2i, i1, i2, 64, 48, nx, 3, 3, 64, 48, 2.4, 1, 1, 0.4, sc, nn, bb);
     }
+    /* fm3d_atan2_cr over every finite magnitude, all quadrants, both orders (from 2^997 on an unscaled
+       Dekker split overflows: the NaN quotient must not index fm3d_cr_atan01's table), a
+       NaN straight into fm3d_cr_atan01, and the other functions of orc_math_eval on special values */
+    {
+        static const double mg[] = {0x1p-500, 0x1p+500, 0x1p-900, 0x1p+900, 0x1p+996, 0x1p+997, 0x1.b5c4a37e91d2fp+997,
+                                    0x1p+1000, 0x1p+1001, 0x1p+1023, 0x1.fffffffffffffp+1023, 1e-300, 0x1p-1022,
+                                    0x1p-1040, 0x0.0000000000001p-1022, 1.0, 0x1.b5c4a37e91d2fp+0};
+        enum { NM = sizeof mg / sizeof mg[0] };
+        static double ys[4 * NM * NM], xs[4 * NM * NM], at[4 * NM * NM];
+        static const double sp[] = {0.0, -0.0, 1.0, -1.5, 3e5, 0x1p+19, 1e22, 1e300, -746.0, 710.0, 0x1p-1074, INFINITY,
+                                    -INFINITY, NAN};
+        enum { NS = sizeof sp / sizeof sp[0] };
+        static double o[NS];
+        int a, b, s, fn;
+        n = 0;
+        for (a = 0; a < NM; a++)
+            for (b = 0; b < NM; b++)
+                for (s = 0; s < 4; s++, n++) {
+                    ys[n] = (s & 1) ? -mg[a] : mg[a];
+                    xs[n] = (s & 2) ? -mg[b] : mg[b];
+                }
+        orc_math_eval(2, ORC_LM_DETMATH, ys, xs, n, at);
+        for (i = 0; i < n; i++) {
+            const double lim = xs[i] < 0 ? 3.2 : 1.6;
+            if (!(fabs(at[i]) <= lim) || !signbit(at[i]) != !signbit(ys[i]) || fabs(at[i] - atan2(ys[i], xs[i])) > 1e-15 * lim) {
+                printf("atan2_cr(%a, %a) = %a\n", ys[i], xs[i], at[i]);
+                return 1;
+            }
+        }
+        if (fm3d_dd_round(fm3d_cr_atan01(fm3d_dd_make(NAN, 0.))) == 0.0) return 1; /* NaN in, NaN out */
+        for (fn = 0; fn <= 7; fn++) {
+            orc_math_eval(fn, ORC_LM_DETMATH, sp, sp, NS, o);
+            orc_math_eval(fn, ORC_LM_DETMATH | ORC_DET_1ULP, sp, sp, NS, o);
+        }
+    }
     /* circular neighbourhoods (given normals and the X/|X| branch) */
     {
         static double X[6] = {0.1, -0.2, 1.9, 0.3, 0.1, 2.1}, N[6] = {0, 0.1, -0.99, 0.2, 0.2, -0.95}, o[2 * 15 * 5 * 3];

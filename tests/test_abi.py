@@ -154,6 +154,14 @@ def test_new_entry_points_reject_bad_arguments(fm3d):
     n = ctypes.c_int(0)
     assert L.fm3d_pipeline_submit_ncc(None, 4, 4, ctypes.c_double(0.4)) == invalid
     assert L.fm3d_pipeline_wait_ncc(None, ctypes.byref(n), None) == invalid
+    # fm3d_math_probe: a null context (whatever else is right), and the table the wrapper mirrors
+    buf = (ctypes.c_double * 4)()
+    assert L.fm3d_math_probe(None, 0, buf, buf, 4, buf) == invalid
+    assert L.fm3d_math_probe(None, len(fm3d.PROBE_FNS), buf, buf, 0, buf) == invalid
+    with open(os.path.join(ROOT, "include", "fm3d.h")) as f:
+        codes = re.findall(r"\bFM3D_PROBE_([A-Z0-9_]+)\b(?=\s*(?:=\s*0)?,)", f.read())
+    assert [c.lower() for c in codes] == list(fm3d.PROBE_FNS)
+    assert fm3d.PROBE_BINARY <= set(fm3d.PROBE_FNS)
 
 
 def test_gravity_and_patch_size_host(fm3d, orc):

@@ -4,45 +4,28 @@ orc_math_eval (the same header the GPU compiles).  CPU only.
 
 Inputs: the ranges the LM feeds them (angles of a few radians, exponents of the LM's weights),
 the reduction's hard cases (multiples of pi/2 rounded to double, the Cody-Waite range's end 2^19),
-signed zeros, subnormals and the axes of atan2.  Every result must be mpmath's value rounded to
-nearest; the 1-ulp polynomials (fm3d_detmath.h, DET_1ULP; the NCC hypotheses) within one ulp."""
+signed zeros, subnormals and the axes of atan2, and for atan2 every magnitude a finite double takes
+(tests/math_cases.py holds the sets; tests/test_gpu_math_probe.py runs them through the device build).
+Every result must be mpmath's value rounded to nearest; the 1-ulp polynomials (fm3d_detmath.h,
+DET_1ULP; the NCC hypotheses) within one ulp."""
 import math
 
 import numpy as np
 import pytest
 
+import math_cases
+
 mpmath = pytest.importorskip("mpmath")
 mp = mpmath.mp
 
 
-def _ref(fn, x, y=None):
-    with mpmath.workprec(200):
-        if fn == "sin":
-            return np.array([float(mpmath.sin(mpmath.mpf(v))) for v in x])
-        if fn == "cos":
-            return np.array([float(mpmath.cos(mpmath.mpf(v))) for v in x])
-        if fn == "exp":
-            return np.array([float(mpmath.exp(mpmath.mpf(v))) for v in x])
-        return np.array([float(mpmath.atan2(mpmath.mpf(a), mpmath.mpf(b))) for a, b in zip(x, y)])
-
-
-def _mismatch(got, ref):
-    """indices where the bits differ (mpmath has no signed zero: a zero matches either zero)"""
-    return np.flatnonzero((got.view(np.int64) != ref.view(np.int64)) & ~((got == 0) & (ref == 0)))
-
-
-def _angles(rng, n):
-    k = np.arange(-40, 41)
-    hard = np.concatenate([k * (np.pi / 2), np.nextafter(k * (np.pi / 2), np.inf), np.nextafter(k * (np.pi / 2), -np.inf)])
-    return np.concatenate([
-        rng.uniform(-4, 4, n), rng.uniform(-100, 100, n // 4), rng.uniform(-2.0 ** 19, 2.0 ** 19, n // 8),
-        hard, [0.0, -0.0, 5e-324, -5e-324, 1e-300, 2.0 ** -30, 0.5, 1.0, 2.0, np.pi, 2.0 ** 19 - 1],
-        np.nextafter(np.float64(2.0 ** 19), 0.0) * np.array([1.0, -1.0])])
+_ref = math_cases.ref_mpmath
+_mismatch = math_cases.mismatch
 
 
 @pytest.mark.parametrize("fn", ["sin", "cos"])
 def test_sin_cos_correctly_rounded(orc, fn):
-    x = _angles(np.random.default_rng(1), 3000)
+    x = math_cases.angles(np.random.default_rng(1), 3000)
     got = orc.math_eval(fn, x)
     ref = _ref(fn, x)
     bad = _mismatch(got, ref)
@@ -58,11 +41,7 @@ def test_sin_cos_correctly_rounded(orc, fn):
 
 
 def test_atan2_correctly_rounded(orc):
-    rng = np.random.default_rng(2)
-    y = np.concatenate([rng.normal(size=3000), rng.normal(size=500) * 1e-8, [0.0, -0.0, 0.0, -0.0, 1.0, -1.0, 0.0, 5e-324],
-                        rng.uniform(-1, 1, 500)])
-    x = np.concatenate([rng.normal(size=3000), rng.normal(size=500), [0.0, 0.0, -0.0, -0.0, 0.0, 0.0, 1.0, -1.0],
-                        rng.uniform(-1, 1, 500) * 1e6])
+    y, x = math_cases.atan2_pairs()
     got = orc.math_eval("atan2", y, x)
     ref = _ref("atan2", y, x)
     axes = (x == 0) | (y == 0)  # signed zeros: IEEE's special values (exact in libm), not mpmath's
@@ -70,12 +49,30 @@ def test_atan2_correctly_rounded(orc):
     bad = _mismatch(got, ref)
     assert bad.size == 0, [(y[i], x[i], got[i], ref[i]) for i in bad[:5]]
     assert math.copysign(1.0, orc.math_eval("atan2", np.array([-0.0]), np.array([1.0]))[0]) == -1.0
+    # every finite magnitude: operands beyond 2^+-500 are scaled before the double-double division
+    # (from 2^997 on an unscaled Dekker split overflows to a NaN quotient, which must not index the table)
+    y, x = math_cases.atan2_extremes()
+    got = orc.math_eval("atan2", y, x)
+    ref = math_cases.atan2_extremes_ref(y, x)
+    bad = math_cases.atan2_extremes_bad(got, ref)
+    assert bad.size == 0, [(float(y[i]).hex(), float(x[i]).hex(), got[i], ref[i]) for i in bad[:5]]
+    assert (np.signbit(got) == np.signbit(y)).all()  # underflowed results keep y's sign
+
+
+def test_sincos_sel_is_sin_and_cos(orc):
+    """fm3d_sincos_sel_cr -- the only sin / cos form the LM kernel calls -- returns fm3d_sin_cr's bits
+    with cosine 0 and fm3d_cos_cr's with cosine 1, the sign of sin(-0) and the arguments beyond 2^19
+    (where all three hand over to fm3d_detmath.h) included"""
+    x = np.concatenate([math_cases.angles(np.random.default_rng(1), 3000), math_cases.angles_beyond()])
+    for sel, fn in (("sincos_sel0", "sin"), ("sincos_sel1", "cos")):
+        a, b = orc.math_eval(sel, x), orc.math_eval(fn, x)
+        same = (a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))
+        assert same.all(), [(x[i], a[i], b[i]) for i in np.flatnonzero(~same)[:5]]
+    assert np.signbit(orc.math_eval("sincos_sel0", np.array([-0.0]))[0])
 
 
 def test_exp_correctly_rounded(orc):
-    rng = np.random.default_rng(3)
-    x = np.concatenate([rng.uniform(-40, 40, 3000), rng.uniform(-1e-3, 1e-3, 300), rng.uniform(-700, 700, 300),
-                        [0.0, -0.0, 1.0, -1.0, 1e-300, -1e-300, 709.0, -700.0]])
+    x = math_cases.exp_args()
     got = orc.math_eval("exp", x)
     ref = _ref("exp", x)
     bad = _mismatch(got, ref)
@@ -96,17 +93,9 @@ def test_hypot_correctly_rounded(orc):
     and the polar factor) -- is mpmath's sqrt(x^2 + y^2) rounded to nearest, over random pairs of
     mixed magnitudes (the DLT's p and beta span many decades), equal pairs, zeros, the 2^-60 cut,
     scaled extremes and non-finite values; glibc's hypot here is not correctly rounded everywhere."""
-    rng = np.random.default_rng(6)
-    n = 6000
-    x = rng.normal(size=n) * 10.0 ** rng.uniform(-12, 12, n)
-    y = rng.normal(size=n) * 10.0 ** rng.uniform(-12, 12, n)
-    hard = np.array([[3.0, 4.0], [1.0, 1.0], [0.0, 0.0], [-0.0, 5.0], [1.0, 2.0 ** -61], [1.0, 2.0 ** -59],
-                     [1e300, 1e300], [1e-300, 3e-300], [5e-324, 5e-324], [1.5e308, 1.5e308], [2.0 ** 500, 1.0]])
-    x = np.concatenate([x, hard[:, 0]])
-    y = np.concatenate([y, hard[:, 1]])
+    x, y, n = math_cases.hypot_pairs()
     got = orc.math_eval("hypot", x, y)
-    with mpmath.workprec(300):
-        ref = np.array([float(mpmath.sqrt(mpmath.mpf(a) ** 2 + mpmath.mpf(b) ** 2)) for a, b in zip(x, y)])
+    ref = _ref("hypot", x, y)
     bad = _mismatch(got, ref)
     assert bad.size == 0, [(x[i], y[i], got[i], ref[i]) for i in bad[:5]]
     inf, nan = float("inf"), float("nan")

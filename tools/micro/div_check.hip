@@ -1,6 +1,9 @@
 // div_check.hip -- the fast divisions of csrc/fm3d_fastdiv.h against the division operator,
 // bit for bit, on random operands (log-uniform exponents across and beyond the guarded
-// ranges, both signs, plus zeros, denormals, infinities and NaNs).
+// ranges, both signs, plus zeros, denormals, infinities and NaNs).  This is the long random run,
+// by hand; the suite checks the same helpers on constructed operands -- quotients next to a
+// rounding midpoint, the guard bounds and their neighbours, waves with one lane outside the
+// guard, partial waves -- in tests/test_gpu_math_probe.py (through fm3d_math_probe).
 //
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I3dfeaturematcher_amd/csrc \
 //         tools/micro/div_check.hip -o tools/micro/div_check && tools/micro/div_check
