@@ -47,6 +47,8 @@ EXPORTS = (
     "fm3d_pipeline_submit_ncc", "fm3d_pipeline_wait_ncc", "fm3d_pipeline_wait_dlt", "fm3d_device_count",
     "fm3d_epipolar_matrix", "fm3d_epipolar_lines", "fm3d_knn2_guided", "fm3d_match_nndr_guided",
     "fm3d_match_mutual", "fm3d_match_mutual_guided", "fm3d_math_probe",
+    "fm3d_verify_matches", "fm3d_ransac_sample", "fm3d_epipolar_from8", "fm3d_epipolar_null8", "fm3d_epipolar_count",
+    "fm3d_pose_from_epipolar",
 )
 
 # include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
@@ -779,6 +781,33 @@ class SingleCameraTriangulator:
         self.ctx.check(lib().fm3d_epipolar_lines(self.ctx.handle, _vp(k1), k1.shape[0], _vp(out)))
         return out
 
+    def verifyMatches(self, kp1, kp2, matches, max_px, hypotheses: int = 1024, seed: int = 0, debug: bool = False):
+        """fm3d_verify_matches: a RANSAC fit of the essential matrix to the matches,
+        `hypotheses` eight-point models scored against every match within max_px pixels -> (E (3, 3),
+        mask (K,) bool, inliers (DMATCH, input order), best); with debug also counts (H,) int32 (-1 for an
+        invalid hypothesis) and models (H, 3, 3).  No valid model: a zero E, no inliers, best -1.  Uses
+        the camera of the context's settings, not g12."""
+        _check_max_px(max_px)
+        H = int(hypotheses)
+        if H < 1:
+            raise Fm3dError(ERR_INVALID, "hypotheses must be >= 1")
+        k1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
+        k2 = np.ascontiguousarray(kp2, dtype=np.float32).reshape(-1, 2)
+        m = np.ascontiguousarray(matches, dtype=DMATCH)
+        K = m.shape[0]
+        E = np.zeros(9)
+        mask = np.zeros(max(K, 1), dtype=np.uint8)
+        out = np.zeros(max(K, 1), dtype=DMATCH)
+        n, best = ctypes.c_int(0), ctypes.c_int(-1)
+        counts = np.zeros(H, dtype=np.int32) if debug else None
+        models = np.zeros((H, 9)) if debug else None
+        self.ctx.check(lib().fm3d_verify_matches(
+            self.ctx.handle, _vp(k1), k1.shape[0], _vp(k2), k2.shape[0], _vp(m), K, H, ctypes.c_double(float(max_px)),
+            ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(E), _ptr(mask, ctypes.c_uint8), _vp(out),
+            ctypes.byref(n), ctypes.byref(best), _vp(counts), _vp(models)))
+        res = (E.reshape(3, 3), mask[:K].astype(bool), out[:n.value].copy(), best.value)
+        return res + (counts, models.reshape(H, 3, 3)) if debug else res
+
     def plane_to_image2(self, X, n):
         """fm3d_plane_to_image2 (device kernel): extractPixelsContour(X) and the level-0 projection of
         those pixels through the plane (X, n) into image 2 -- (image-1 pixels (m, 2), image-2 uv
@@ -1264,6 +1293,67 @@ def epipolar_matrix(g12) -> np.ndarray:
     E = np.zeros(9)
     _check(lib().fm3d_epipolar_matrix(_ptr(np.ascontiguousarray(g12, dtype=np.float64).ravel()), _ptr(E)))
     return E.reshape(3, 3)
+
+
+def ransac_sample(seed: int, h: int, M: int):
+    """fm3d_ransac_sample: the eight distinct match indices of hypothesis h among M matches (host only)
+    -> (idx (8,) int32, valid)."""
+    idx = np.zeros(8, dtype=np.int32)
+    rc = lib().fm3d_ransac_sample(ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_int(h), ctypes.c_int(M),
+                                  _ptr(idx, ctypes.c_int32))
+    if rc < 0:
+        _check(rc)
+    return idx, rc == 0
+
+
+def _pairs(x, n=None):
+    a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 2)
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f"expected {n} points, got {a.shape[0]}")
+    return a
+
+
+def epipolar_from8(x1, x2, null_vector: bool = False):
+    """fm3d_epipolar_from8: the essential matrix (x2^T E x1 = 0) of eight pairs of normalised
+    coordinates (host only) -> (E (3, 3), valid); an invalid model is zero.  null_vector: the unit null
+    vector of the 8 x 9 system before the projection (fm3d_epipolar_null8)."""
+    a, b = _pairs(x1, 8), _pairs(x2, 8)
+    E = np.zeros(9)
+    f = lib().fm3d_epipolar_null8 if null_vector else lib().fm3d_epipolar_from8
+    rc = f(_ptr(a), _ptr(b), _ptr(E))
+    if rc < 0:
+        _check(rc)
+    return E.reshape(3, 3), rc == 0
+
+
+def epipolar_count(E, x1, x2, tau: float):
+    """fm3d_epipolar_count: the pairs within tau (normalised units) of the model by the Sampson test
+    (host only) -> (count, mask (n,) bool)."""
+    a, b = _pairs(x1), _pairs(x2)
+    if a.shape != b.shape:
+        raise ValueError("x1 and x2 differ in length")
+    mask = np.zeros(max(a.shape[0], 1), dtype=np.uint8)
+    rc = lib().fm3d_epipolar_count(_ptr(np.ascontiguousarray(E, dtype=np.float64).ravel()), _ptr(a), _ptr(b),
+                                   a.shape[0], ctypes.c_double(float(tau)), _ptr(mask, ctypes.c_uint8))
+    if rc < 0:
+        _check(rc)
+    return rc, mask[:a.shape[0]].astype(bool)
+
+
+def pose_from_epipolar(E, x1, x2, baseline: float = 1.0):
+    """fm3d_pose_from_epipolar: the decomposition of E that puts most pairs in front of both cameras
+    (host only) -> (g12 (4, 4) = [R | baseline t], votes (4,) int32, valid)."""
+    a, b = _pairs(x1), _pairs(x2)
+    if a.shape != b.shape:
+        raise ValueError("x1 and x2 differ in length")
+    g = np.zeros(16)
+    votes = np.zeros(4, dtype=np.int32)
+    rc = lib().fm3d_pose_from_epipolar(_ptr(np.ascontiguousarray(E, dtype=np.float64).ravel()), _ptr(a), _ptr(b),
+                                       a.shape[0], ctypes.c_double(float(baseline)), _ptr(g),
+                                       _ptr(votes, ctypes.c_int32))
+    if rc < 0:
+        _check(rc)
+    return g.reshape(4, 4), votes, rc == 0
 
 
 class MOSAIC:

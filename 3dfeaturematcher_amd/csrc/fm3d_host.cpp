@@ -2605,6 +2605,8 @@ int fm3d_internal_finish(fm3d_ctx* c, int* nKept, fm3d_pipeline_stats* stats) {
 const int* fm3d_internal_kept_dev(fm3d_ctx* c) { return c->pcnt.as<int>() + 2; }
 hipStream_t fm3d_internal_stream(fm3d_ctx* c) { return c->stream; }
 int fm3d_internal_device(fm3d_ctx* c) { return c->device; }
+const fm3d_settings* fm3d_internal_settings(const fm3d_ctx* c) { return &c->s; }
+int fm3d_internal_fail(fm3d_ctx* c, int code, const char* msg) { return fail(c, code, msg); }
 // the device memory one context may take: its largest LM launch's slabs (every CU filled) plus the
 // per-pair buffers of nA queries against nB train rows of dim elements (a conservative estimate of
 // what the pipeline's DevBufs grow to: descriptors, their u8 / unpacked copies, per-query match,

@@ -324,6 +324,18 @@ void launch_compact_points(const double* in, const int* flag, int n, const int* 
                            int* srcIndex, void* tmp, hipStream_t s);
 void launch_exclusive_scan(const int* flag, int n, int* offsets, int* total, void* tmp, hipStream_t s);
 
+// ---------------- geometric verification (fm3d_verify.hip) ----------------
+constexpr int kVerifyTile = 1024;         // matches per scoring workgroup
+constexpr int kVerifyMaxHyps = 1 << 20;   // hypotheses of one call
+int verify_pad(int M);                    // M rounded up to whole tiles
+// The whole stage on device inputs, queued on s: coordinates (xy: 4 x verify_pad(M) doubles), H
+// hypotheses (models H x 9, count H: -1 for an invalid one), their scores, the best (best, E[9]: -1 and
+// zeros when none is valid) and its inlier mask (flag M ints for the compaction, mask M bytes).
+// M >= 8, 1 <= H <= kVerifyMaxHyps, every match index inside its keypoint array.
+void launch_verify(const Camera& cam, const fm3d_point2f* kp1, const fm3d_point2f* kp2, const fm3d_dmatch* matches,
+                   int M, int H, unsigned long long seed, double tau2, int nCU, double* xy, double* models, int* count,
+                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s);
+
 // ---------------- triangulation ----------------
 struct TriParams {
     Camera cam;

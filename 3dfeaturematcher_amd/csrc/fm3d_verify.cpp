@@ -1,0 +1,214 @@
+// fm3d_verify.cpp -- geometric verification, the host side: fm3d_verify_matches'
+// orchestration and the context-free algebra (sampler, eight-point model, count, pose from E).
+// The arithmetic is include/fm3d_epi8.h's; the kernels are fm3d_verify.hip's.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "fm3d.h"
+#include "fm3d_epi8.h"
+#include "fm3d_internal.h"
+#include "fm3d_kernels.h"
+
+namespace {
+
+#define VCHK(ctx, expr)                                                                                  \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) {                                                                          \
+            if (pool) hipFree(pool);                                                                     \
+            return fm3d_internal_fail((ctx), FM3D_ERR_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
+        }                                                                                                \
+    } while (0)
+
+// one allocation per call, carved in 256-byte steps (the stage keeps nothing in the context)
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+};
+
+double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+void cross3(const double a[3], const double b[3], double c[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+}  // namespace
+
+int fm3d_ransac_sample(uint64_t seed, int h, int M, int32_t idx[8]) {
+    if (!idx || h < 0 || M < 0) return FM3D_ERR_INVALID;
+    int s[8];
+    const bool ok = fm3d_epi8::sample8(seed, (uint32_t)h, (uint32_t)M, s);
+    for (int k = 0; k < 8; k++) idx[k] = s[k];
+    return ok ? 0 : 1;
+}
+
+int fm3d_epipolar_from8(const double x1[16], const double x2[16], double E[9]) {
+    if (!x1 || !x2 || !E) return FM3D_ERR_INVALID;
+    fm3d_epi8::Mat89 A;
+    for (int k = 0; k < 8; k++) fm3d_epi8::set_row(A, k, x1[2 * k], x1[2 * k + 1], x2[2 * k], x2[2 * k + 1]);
+    double e[9];
+    return fm3d_epi8::model8(A, E, e) ? 0 : 1;
+}
+
+int fm3d_epipolar_null8(const double x1[16], const double x2[16], double e[9]) {
+    if (!x1 || !x2 || !e) return FM3D_ERR_INVALID;
+    fm3d_epi8::Mat89 A;
+    for (int k = 0; k < 8; k++) fm3d_epi8::set_row(A, k, x1[2 * k], x1[2 * k + 1], x2[2 * k], x2[2 * k + 1]);
+    if (fm3d_epi8::null8(A, e)) return 0;
+    for (int k = 0; k < 9; k++) e[k] = 0.;
+    return 1;
+}
+
+int fm3d_epipolar_count(const double E[9], const double* x1, const double* x2, int n, double tau, uint8_t* mask) {
+    if (!E || n < 0 || ((!x1 || !x2) && n)) return FM3D_ERR_INVALID;
+    const double tau2 = tau * tau;
+    int cnt = 0;
+    for (int i = 0; i < n; i++) {
+        const bool in = fm3d_epi8::inlier(E, x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1], tau2);
+        if (mask) mask[i] = in ? 1 : 0;
+        cnt += in;
+    }
+    return cnt;
+}
+
+int fm3d_pose_from_epipolar(const double E[9], const double* x1, const double* x2, int n, double baseline,
+                            double g12[16], int32_t votes[4]) {
+    if (!E || !g12 || n < 0 || ((!x1 || !x2) && n)) return FM3D_ERR_INVALID;
+    double u[3][3], v[3][3], W[3];
+    {
+        double u2[2][3], v2[2][3];
+        if (!fm3d_epi8::svd_e(E, u2, v2, W)) return 1;
+        std::memcpy(u, u2, sizeof(u2));
+        std::memcpy(v, v2, sizeof(v2));
+    }
+    cross3(u[0], u[1], u[2]);
+    cross3(v[0], v[1], v[2]);
+    // U W V^T = u1 v0^T - u0 v1^T + u2 v2^T and U W^T V^T = -u1 v0^T + u0 v1^T + u2 v2^T
+    double R[2][9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            R[0][r * 3 + c] = (u[1][r] * v[0][c] + (-u[0][r]) * v[1][c]) + u[2][r] * v[2][c];
+            R[1][r * 3 + c] = ((-u[1][r]) * v[0][c] + u[0][r] * v[1][c]) + u[2][r] * v[2][c];
+        }
+    int vt[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4; k++) {
+        const double* Rk = R[k >> 1];
+        const double sg = (k & 1) ? -1. : 1.;
+        const double t[3] = {sg * u[2][0], sg * u[2][1], sg * u[2][2]};
+        for (int i = 0; i < n; i++) {
+            const double p[3] = {x1[2 * i], x1[2 * i + 1], 1.}, b[3] = {x2[2 * i], x2[2 * i + 1], 1.};
+            const double a[3] = {dot3(Rk, p), dot3(Rk + 3, p), dot3(Rk + 6, p)};
+            const double aa = dot3(a, a), ab = dot3(a, b), bb = dot3(b, b), at = dot3(a, t), bt = dot3(b, t);
+            const double det = aa * bb - ab * ab;
+            const double z1 = (ab * bt - bb * at) / det, z2 = (aa * bt - ab * at) / det;
+            vt[k] += (z1 > 0. && z2 > 0.) ? 1 : 0;
+        }
+    }
+    int bk = 0;
+    for (int k = 1; k < 4; k++)
+        if (vt[k] > vt[bk]) bk = k;
+    const double* Rb = R[bk >> 1];
+    const double sg = (bk & 1) ? -1. : 1.;
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) g12[r * 4 + c] = Rb[r * 3 + c];
+        g12[r * 4 + 3] = baseline * (sg * u[2][r]);
+    }
+    g12[12] = g12[13] = g12[14] = 0.;
+    g12[15] = 1.;
+    if (votes)
+        for (int k = 0; k < 4; k++) votes[k] = vt[k];
+    return 0;
+}
+
+int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm3d_point2f* kpts2, int n2,
+                        const fm3d_dmatch* matches, int nMatches, int hypotheses, double maxPx, uint64_t seed,
+                        double E[9], uint8_t* inlierMask, fm3d_dmatch* inliers, int* nInliers, int* best,
+                        int32_t* counts, double* models) {
+    const int M = nMatches, H = hypotheses;
+    if (!c || !E || !nInliers || !best || n1 < 0 || n2 < 0 || M < 0 || (!kpts1 && n1) || (!kpts2 && n2) ||
+        ((!matches || !inlierMask || !inliers) && M))
+        return fm3d_internal_fail(c, FM3D_ERR_INVALID, "null argument");
+    if (H < 1) return fm3d_internal_fail(c, FM3D_ERR_INVALID, "hypotheses must be >= 1");
+    if (!(maxPx > 0. && maxPx <= DBL_MAX)) return fm3d_internal_fail(c, FM3D_ERR_INVALID, "maxPx must be finite and > 0");
+    for (int i = 0; i < M; i++)
+        if (matches[i].queryIdx < 0 || matches[i].queryIdx >= n1 || matches[i].trainIdx < 0 || matches[i].trainIdx >= n2)
+            return fm3d_internal_fail(c, FM3D_ERR_INVALID, "match index out of range");
+    if (H > fm3d::kVerifyMaxHyps) return fm3d_internal_fail(c, FM3D_ERR_UNSUPPORTED, "more than 2^20 hypotheses");
+
+    for (int k = 0; k < 9; k++) E[k] = 0.;
+    *nInliers = 0;
+    *best = -1;
+    if (M) std::memset(inlierMask, 0, (size_t)M);
+    if (M < 8) {  // no sample exists: every hypothesis is invalid
+        if (counts)
+            for (int h = 0; h < H; h++) counts[h] = -1;
+        if (models) std::memset(models, 0, (size_t)H * 9 * sizeof(double));
+        return FM3D_OK;
+    }
+
+    const fm3d_settings* S = fm3d_internal_settings(c);
+    fm3d::Camera cam{};
+    cam.fx = S->Fx;
+    cam.fy = S->Fy;
+    cam.cx = S->Cx;
+    cam.cy = S->Cy;
+    cam.k[0] = S->k0;
+    cam.k[1] = S->k1;
+    cam.k[2] = S->p1;
+    cam.k[3] = S->p2;
+    cam.k[4] = S->k2;
+    const double tau = maxPx * 2.0 / (cam.fx + cam.fy);
+    const double tau2 = tau * tau;
+
+    char* pool = nullptr;
+    hipStream_t st = fm3d_internal_stream(c);
+    VCHK(c, hipSetDevice(fm3d_internal_device(c)));
+    int nCU = 0;
+    VCHK(c, hipDeviceGetAttribute(&nCU, hipDeviceAttributeMultiprocessorCount, fm3d_internal_device(c)));
+    const int Mpad = fm3d::verify_pad(M);
+    Carver cv;
+    const size_t oK1 = cv.take((size_t)n1 * sizeof(fm3d_point2f)), oK2 = cv.take((size_t)n2 * sizeof(fm3d_point2f));
+    const size_t oM = cv.take((size_t)M * sizeof(fm3d_dmatch)), oXY = cv.take((size_t)4 * Mpad * sizeof(double));
+    const size_t oMod = cv.take((size_t)H * 9 * sizeof(double)), oCnt = cv.take((size_t)H * sizeof(int));
+    const size_t oBest = cv.take(sizeof(int)), oE = cv.take(9 * sizeof(double));
+    const size_t oFlag = cv.take((size_t)M * sizeof(int)), oMask = cv.take((size_t)M);
+    const size_t oOut = cv.take((size_t)(M + 1) * sizeof(fm3d_dmatch)), oN = cv.take(sizeof(int));
+    const size_t oTmp = cv.take(fm3d::scan_tmp_bytes(M));
+    VCHK(c, hipMalloc((void**)&pool, cv.off));
+    VCHK(c, hipMemcpyAsync(pool + oK1, kpts1, (size_t)n1 * sizeof(fm3d_point2f), hipMemcpyHostToDevice, st));
+    VCHK(c, hipMemcpyAsync(pool + oK2, kpts2, (size_t)n2 * sizeof(fm3d_point2f), hipMemcpyHostToDevice, st));
+    VCHK(c, hipMemcpyAsync(pool + oM, matches, (size_t)M * sizeof(fm3d_dmatch), hipMemcpyHostToDevice, st));
+    fm3d::launch_verify(cam, (const fm3d_point2f*)(pool + oK1), (const fm3d_point2f*)(pool + oK2),
+                        (const fm3d_dmatch*)(pool + oM), M, H, seed, tau2, nCU, (double*)(pool + oXY),
+                        (double*)(pool + oMod), (int*)(pool + oCnt), (int*)(pool + oBest), (double*)(pool + oE),
+                        (int*)(pool + oFlag), (uint8_t*)(pool + oMask), st);
+    fm3d::launch_compact_dmatch((const fm3d_dmatch*)(pool + oM), (const int*)(pool + oFlag), M,
+                                (fm3d_dmatch*)(pool + oOut), (int*)(pool + oN), pool + oTmp, st);
+    VCHK(c, hipGetLastError());
+    int n = 0;
+    VCHK(c, hipMemcpyAsync(&n, pool + oN, sizeof(int), hipMemcpyDeviceToHost, st));
+    VCHK(c, hipMemcpyAsync(best, pool + oBest, sizeof(int), hipMemcpyDeviceToHost, st));
+    VCHK(c, hipMemcpyAsync(E, pool + oE, 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+    VCHK(c, hipMemcpyAsync(inlierMask, pool + oMask, (size_t)M, hipMemcpyDeviceToHost, st));
+    if (counts) VCHK(c, hipMemcpyAsync(counts, pool + oCnt, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (models) VCHK(c, hipMemcpyAsync(models, pool + oMod, (size_t)H * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+    VCHK(c, hipStreamSynchronize(st));
+    if (n < 0 || n > M) {
+        hipFree(pool);
+        return fm3d_internal_fail(c, FM3D_ERR_HIP, "verify: inlier count out of range");
+    }
+    if (n) VCHK(c, hipMemcpy(inliers, pool + oOut, (size_t)n * sizeof(fm3d_dmatch), hipMemcpyDeviceToHost));
+    *nInliers = n;
+    hipFree(pool);
+    return FM3D_OK;
+}

@@ -307,6 +307,45 @@ int fm3d_epipolar_lines(fm3d_ctx *ctx, const fm3d_point2f *kpts1, int n1, float 
 int fm3d_triangulate(fm3d_ctx *ctx, const fm3d_point2f *kpts1, int n1, const fm3d_point2f *kpts2, int n2,
                      const fm3d_dmatch *matches, int nMatches, double *points, uint8_t *inlierMask, int *nPoints);
 
+/* ---------------- geometric verification ---------------- */
+/* RANSAC fit of the essential matrix to the matches themselves (no reference counterpart; needs the
+   camera of the context's settings, not g12).  Hypothesis h = 0 .. hypotheses-1 takes the eight
+   matches fm3d_ransac_sample(seed, h, nMatches) names, fits fm3d_epipolar_from8 to their undistorted
+   normalised coordinates (kept as doubles) and counts the matches within maxPx pixels (the unit of
+   fm3d_knn2_guided: tau = maxPx * 2 / (Fx + Fy)) by the Sampson test of fm3d_epipolar_count.  The best
+   is the largest count, the lowest h on ties.  E: its row-major model; inlierMask: nMatches bytes;
+   inliers (capacity nMatches): the input matches it accepts, in their order; *best: its index.
+   nMatches < 8 or no valid hypothesis: *best = -1, E zero, no inliers, FM3D_OK.  counts (hypotheses
+   int32, -1 for an invalid hypothesis) and models (hypotheses x 9) may be NULL.  Results depend on the
+   inputs and the seed alone.  FM3D_ERR_INVALID, before any launch: a null required pointer,
+   hypotheses < 1, maxPx not finite or not > 0, a match index outside [0, n1) / [0, n2);
+   FM3D_ERR_UNSUPPORTED: more than 2^20 hypotheses. */
+int fm3d_verify_matches(fm3d_ctx *ctx, const fm3d_point2f *kpts1, int n1, const fm3d_point2f *kpts2, int n2,
+                        const fm3d_dmatch *matches, int nMatches, int hypotheses, double maxPx, uint64_t seed,
+                        double E[9], uint8_t *inlierMask, fm3d_dmatch *inliers, int *nInliers, int *best,
+                        int32_t *counts, double *models);
+/* The stage's algebra on the host (no context, usable without a GPU), the same code the kernels run.
+   fm3d_ransac_sample: the eight distinct indices in [0, M) of hypothesis h; returns 1 (idx partly -1)
+   when 64 draws give fewer, as every M < 8 does.
+   fm3d_epipolar_from8: the essential matrix of eight pairs (x1, x2: 8 x (x, y) normalised
+   coordinates, x2^T E x1 = 0) -- the null vector of the 8 x 9 system by Gauss-Jordan elimination with
+   full pivoting, then singular values (1, 1, 0) on its singular vectors; returns 1 and a zero E when
+   invalid (a zero or non-finite pivot, a second singular value <= DBL_MIN).
+   fm3d_epipolar_null8: that null vector before the projection (unit length); 1 and zeros when invalid.
+   fm3d_epipolar_count: the number of the n pairs with r^2 <= tau^2 den, den > 0 (Sampson's distance
+   without the division; tau in normalised units); mask (n bytes) may be NULL.
+   fm3d_pose_from_epipolar: the (R, t) among E's four decompositions that puts most of the n pairs in
+   front of both cameras (votes[4], may be NULL: per candidate (U W V^T, +t), (U W V^T, -t),
+   (U W^T V^T, +t), (U W^T V^T, -t), t = u0 x u1; the lowest index on ties) as g12 = [R | baseline t],
+   ready for fm3d_set_g12; returns 1 when E's second singular value is <= DBL_MIN.
+   FM3D_ERR_INVALID: a null pointer, a negative h, M or n. */
+int fm3d_ransac_sample(uint64_t seed, int h, int M, int32_t idx[8]);
+int fm3d_epipolar_from8(const double x1[16], const double x2[16], double E[9]);
+int fm3d_epipolar_null8(const double x1[16], const double x2[16], double e[9]);
+int fm3d_epipolar_count(const double E[9], const double *x1, const double *x2, int n, double tau, uint8_t *mask);
+int fm3d_pose_from_epipolar(const double E[9], const double *x1, const double *x2, int n, double baseline,
+                            double g12[16], int32_t votes[4]);
+
 /* ---------------- NormalOptimizer ---------------- */
 /* setImages (normaloptimizer.cpp:191-221): 8-bit gray images, builds both pyramids */
 int fm3d_set_images(fm3d_ctx *ctx, const uint8_t *img1, const uint8_t *img2, int width, int height, int stride);

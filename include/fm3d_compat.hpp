@@ -270,6 +270,33 @@ public:
         for (int i = 0; i < n; i++) points3D.push_back(Vec3d{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]});
         for (int i = 0; i < K; i++) outliersMask.push_back(mask[i] != 0);
     }
+    // Geometric verification (no reference counterpart): a RANSAC fit of the
+    // essential matrix to the matches; inliers is cleared then filled with the matches within maxPx
+    // pixels of the best of `hypotheses` eight-point models (input order), E its row-major model
+    // (zero, and no inliers, when no model is valid).  Returns the best hypothesis's index or -1.
+    // Uses the camera of the device's settings, not g12.
+    int verifyMatches(const std::vector<KeyPoint>& k1, const std::vector<KeyPoint>& k2,
+                      const std::vector<DMatch>& matches, double maxPx, std::vector<DMatch>& inliers,
+                      std::array<double, 9>& E, int hypotheses = 1024, uint64_t seed = 0,
+                      std::vector<bool>* inlierMask = nullptr) {
+        std::vector<fm3d_point2f> a(k1.size()), b(k2.size());
+        for (size_t i = 0; i < k1.size(); i++) a[i] = fm3d_point2f{k1[i].pt.x, k1[i].pt.y};
+        for (size_t i = 0; i < k2.size(); i++) b[i] = fm3d_point2f{k2[i].pt.x, k2[i].pt.y};
+        const int K = (int)matches.size();
+        std::vector<uint8_t> mask(K > 0 ? K : 1);
+        std::vector<DMatch> kept(K > 0 ? K : 1);
+        int n = 0, best = -1;
+        check(d_.ctx(), fm3d_verify_matches(d_.ctx(), a.data(), (int)a.size(), b.data(), (int)b.size(), matches.data(), K,
+                                            hypotheses, maxPx, seed, E.data(), mask.data(), kept.data(), &n, &best,
+                                            nullptr, nullptr));
+        kept.resize(n);
+        inliers.swap(kept);
+        if (inlierMask) {
+            inlierMask->clear();
+            for (int i = 0; i < K; i++) inlierMask->push_back(mask[i] != 0);
+        }
+        return best;
+    }
     Device& device() const { return d_; }
 
 private:

@@ -1,0 +1,199 @@
+/*
+ * fm3d_epi8.h -- the arithmetic of the geometric verification, host and device.
+ *
+ * A RANSAC fit of the essential matrix to matches: a counter-based sampler, the eight-point null
+ * vector by Gauss-Jordan elimination with full pivoting, the projection onto the essential manifold
+ * by OpenCV 2.4's JacobiSVD (fm3d_cvsvd.h) and the Sampson test without a division.  Everything is
+ * fp64 in the operand order written here, compiled without FMA contraction, so the host library, the
+ * kernels of fm3d_verify.hip and the numpy restatement (tests/verify_pyref.py) give the same bits.
+ * This header is the only place the arithmetic lives.
+ */
+#ifndef FM3D_EPI8_H
+#define FM3D_EPI8_H
+
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "fm3d_cvsvd.h"
+
+namespace fm3d_epi8 {
+
+constexpr int kAttempts = 64;  // draws per hypothesis
+
+// draw a of hypothesis h: splitmix64's finaliser over a Weyl counter, then the top 32 bits scaled
+// to [0, M) (M < 2^31)
+FM3D_CVSVD_HD uint32_t draw(uint64_t seed, uint32_t h, int a, uint32_t M) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (1ull + 64ull * (uint64_t)h + (uint64_t)a);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (uint32_t)(((z >> 32) * (uint64_t)M) >> 32);
+}
+
+// the first eight distinct draws of hypothesis h; false when 64 attempts give fewer (M < 8 always)
+FM3D_CVSVD_HD bool sample8(uint64_t seed, uint32_t h, uint32_t M, int idx[8]) {
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) idx[k] = -1;
+    if (M < 8) return false;
+    for (int a = 0; a < kAttempts && n < 8; a++) {
+        const int v = (int)draw(seed, h, a, M);
+        bool fresh = true;
+#pragma unroll
+        for (int k = 0; k < 8; k++) fresh = fresh && idx[k] != v;
+        if (fresh) {
+            // idx[n] = v with n a run-time index: a select per slot keeps idx in registers
+#pragma unroll
+            for (int k = 0; k < 8; k++) idx[k] = k == n ? v : idx[k];
+            n++;
+        }
+    }
+    return n == 8;
+}
+
+// the 8 x 9 system on the host: a plain array (the hypothesis kernel keeps its own in LDS)
+struct Mat89 {
+    double a[72];
+    FM3D_CVSVD_HD double& operator()(int r, int c) { return a[r * 9 + c]; }
+};
+
+// row k of the system from the pair (x1, y1) <-> (x2, y2): e is the row-major E of x2^T E x1 = 0
+template <typename Mat>
+FM3D_CVSVD_HD void set_row(Mat& A, int k, double x1, double y1, double x2, double y2) {
+    A(k, 0) = x2 * x1;
+    A(k, 1) = x2 * y1;
+    A(k, 2) = x2;
+    A(k, 3) = y2 * x1;
+    A(k, 4) = y2 * y1;
+    A(k, 5) = y2;
+    A(k, 6) = x1;
+    A(k, 7) = y1;
+    A(k, 8) = 1.;
+}
+
+// The unit null vector of the 8 x 9 system by Gauss-Jordan elimination with full pivoting (A is
+// destroyed).  Step s: the pivot is the entry of largest magnitude in rows s..7 over the columns
+// not yet chosen, the first met in row-then-column order on ties (a NaN is never larger); no pivot,
+// a zero or a non-finite one: false.  Rows swapped, every other row reduced over all nine columns.
+// x[free] = 1, x[c_s] = -A[s][free] / A[s][c_s] on the final A, scaled by 1 / sqrt(sum of squares in
+// index order); a sum that is not finite: false.
+template <typename Mat>
+FM3D_CVSVD_HD bool null8(Mat& A, double e[9]) {
+    int col[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned used = 0;
+    for (int s = 0; s < 8; s++) {
+        double best = -1.;
+        int br = -1, bc = -1;
+        for (int r = s; r < 8; r++)
+            for (int c = 0; c < 9; c++) {
+                if (used >> c & 1u) continue;
+                const double v = fabs(A(r, c));
+                if (v > best) {
+                    best = v;
+                    br = r;
+                    bc = c;
+                }
+            }
+        if (br < 0) return false;
+        const double p = A(br, bc);
+        if (p == 0. || !(fabs(p) <= DBL_MAX)) return false;
+        if (br != s)
+            for (int j = 0; j < 9; j++) {
+                const double t = A(s, j);
+                A(s, j) = A(br, j);
+                A(br, j) = t;
+            }
+        for (int r = 0; r < 8; r++) {
+            if (r == s) continue;
+            const double f = A(r, bc) / p;
+            if (f != 0.)
+                for (int j = 0; j < 9; j++) A(r, j) = A(r, j) - f * A(s, j);
+        }
+        used |= 1u << bc;
+#pragma unroll
+        for (int k = 0; k < 8; k++) col[k] = k == s ? bc : col[k];
+    }
+    int fr = 0;
+#pragma unroll
+    for (int c = 0; c < 9; c++)
+        if (!(used >> c & 1u)) fr = c;
+    double x[9];
+#pragma unroll
+    for (int c = 0; c < 9; c++) x[c] = 1.;
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        const double v = -A(s, fr) / A(s, col[s]);
+#pragma unroll
+        for (int c = 0; c < 9; c++) x[c] = c == col[s] ? v : x[c];
+    }
+    double ss = 0.;
+#pragma unroll
+    for (int c = 0; c < 9; c++) ss += x[c] * x[c];
+    if (!(ss <= DBL_MAX)) return false;
+    const double inv = 1. / sqrt(ss);
+#pragma unroll
+    for (int c = 0; c < 9; c++) e[c] = x[c] * inv;
+    return true;
+}
+
+// The left and right singular vectors of a row-major 3 x 3 E in fm3d_cv::jacobi_svd's sorted order:
+// u_i = At[perm[i]] * (1 / W[i]) for i = 0, 1 and v_i = Vt[perm[i]].  False unless W[1] > DBL_MIN.
+FM3D_CVSVD_HD bool svd_e(const double E[9], double (&u)[2][3], double (&v)[2][3], double (&W)[3]) {
+    double At[3][3], Vt[3][3];
+    int perm[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) At[i][k] = E[k * 3 + i];
+    fm3d_cv::jacobi_svd<3, 3>(At, W, Vt, perm);
+    if (!(W[1] > DBL_MIN)) return false;
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        double a[3];
+        fm3d_cv::pick_row<3, 3>(At, perm[i], a);
+        fm3d_cv::pick_row<3, 3>(Vt, perm[i], v[i]);
+        const double s = 1. / W[i];
+#pragma unroll
+        for (int k = 0; k < 3; k++) u[i][k] = a[k] * s;
+    }
+    return true;
+}
+
+// the nearest essential matrix in shape: singular values (1, 1, 0) on e's singular vectors
+FM3D_CVSVD_HD bool project_essential(const double e[9], double E[9]) {
+    double u[2][3], v[2][3], W[3];
+    if (!svd_e(e, u, v, W)) return false;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) E[r * 3 + c] = u[0][r] * v[0][c] + u[1][r] * v[1][c];
+    return true;
+}
+
+// the model of eight pairs whose rows are already in A; an invalid one is all zero (false)
+template <typename Mat>
+FM3D_CVSVD_HD bool model8(Mat& A, double E[9], double e[9]) {
+    const bool ok = null8(A, e) && project_essential(e, E);
+    if (!ok) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) E[k] = 0.;
+    }
+    return ok;
+}
+
+// Sampson's test without the division: r^2 <= tau2 * den with den > 0 (a NaN fails)
+FM3D_CVSVD_HD bool inlier(const double E[9], double x1, double y1, double x2, double y2, double tau2) {
+    const double l0 = (E[0] * x1 + E[1] * y1) + E[2];
+    const double l1 = (E[3] * x1 + E[4] * y1) + E[5];
+    const double l2 = (E[6] * x1 + E[7] * y1) + E[8];
+    const double m0 = (E[0] * x2 + E[3] * y2) + E[6];
+    const double m1 = (E[1] * x2 + E[4] * y2) + E[7];
+    const double r = (x2 * l0 + y2 * l1) + l2;
+    const double den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
+    return (den > 0.) & (r * r <= tau2 * den);  // both evaluated: no branch per pair in the scoring loop
+}
+
+}  // namespace fm3d_epi8
+
+#endif /* FM3D_EPI8_H */
