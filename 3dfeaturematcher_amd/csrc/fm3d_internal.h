@@ -21,10 +21,6 @@ int fm3d_internal_finish(fm3d_ctx* c, int* nKept, fm3d_pipeline_stats* stats);
 // the survivor count of the queued run on the device (valid in stream order after the run)
 const int* fm3d_internal_kept_dev(fm3d_ctx* c);
 hipStream_t fm3d_internal_stream(fm3d_ctx* c);
-int fm3d_internal_device(fm3d_ctx* c);
-// the settings the context was created with (its camera), and fm3d_last_error's text with a code
-const fm3d_settings* fm3d_internal_settings(const fm3d_ctx* c);
-int fm3d_internal_fail(fm3d_ctx* c, int code, const char* msg);
 int fm3d_internal_prepare(fm3d_ctx* c);
 // the device memory one context of this settings may grow to for a frame pair of nA x nB rows:
 // its LM slabs (the largest launch) + a conservative estimate of the per-pair buffers

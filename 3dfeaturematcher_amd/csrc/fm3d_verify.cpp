@@ -9,20 +9,13 @@
 #include <string>
 
 #include "fm3d.h"
+#include "fm3d_ctx.h"
 #include "fm3d_epi8.h"
-#include "fm3d_internal.h"
 #include "fm3d_kernels.h"
 
-namespace {
+using namespace fm3d_host;
 
-#define VCHK(ctx, expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) {                                                                          \
-            if (pool) hipFree(pool);                                                                     \
-            return fm3d_internal_fail((ctx), FM3D_ERR_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-        }                                                                                                \
-    } while (0)
+namespace {
 
 // one allocation per call, carved in 256-byte steps (the stage keeps nothing in the context)
 struct Carver {
@@ -137,13 +130,13 @@ int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm
     const int M = nMatches, H = hypotheses;
     if (!c || !E || !nInliers || !best || n1 < 0 || n2 < 0 || M < 0 || (!kpts1 && n1) || (!kpts2 && n2) ||
         ((!matches || !inlierMask || !inliers) && M))
-        return fm3d_internal_fail(c, FM3D_ERR_INVALID, "null argument");
-    if (H < 1) return fm3d_internal_fail(c, FM3D_ERR_INVALID, "hypotheses must be >= 1");
-    if (!(maxPx > 0. && maxPx <= DBL_MAX)) return fm3d_internal_fail(c, FM3D_ERR_INVALID, "maxPx must be finite and > 0");
+        return fail(c, FM3D_ERR_INVALID, "null argument");
+    if (H < 1) return fail(c, FM3D_ERR_INVALID, "hypotheses must be >= 1");
+    if (!(maxPx > 0. && maxPx <= DBL_MAX)) return fail(c, FM3D_ERR_INVALID, "maxPx must be finite and > 0");
     for (int i = 0; i < M; i++)
         if (matches[i].queryIdx < 0 || matches[i].queryIdx >= n1 || matches[i].trainIdx < 0 || matches[i].trainIdx >= n2)
-            return fm3d_internal_fail(c, FM3D_ERR_INVALID, "match index out of range");
-    if (H > fm3d::kVerifyMaxHyps) return fm3d_internal_fail(c, FM3D_ERR_UNSUPPORTED, "more than 2^20 hypotheses");
+            return fail(c, FM3D_ERR_INVALID, "match index out of range");
+    if (H > fm3d::kVerifyMaxHyps) return fail(c, FM3D_ERR_UNSUPPORTED, "more than 2^20 hypotheses");
 
     for (int k = 0; k < 9; k++) E[k] = 0.;
     *nInliers = 0;
@@ -156,25 +149,14 @@ int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm
         return FM3D_OK;
     }
 
-    const fm3d_settings* S = fm3d_internal_settings(c);
-    fm3d::Camera cam{};
-    cam.fx = S->Fx;
-    cam.fy = S->Fy;
-    cam.cx = S->Cx;
-    cam.cy = S->Cy;
-    cam.k[0] = S->k0;
-    cam.k[1] = S->k1;
-    cam.k[2] = S->p1;
-    cam.k[3] = S->p2;
-    cam.k[4] = S->k2;
+    const fm3d::Camera& cam = c->cam;
     const double tau = maxPx * 2.0 / (cam.fx + cam.fy);
     const double tau2 = tau * tau;
 
-    char* pool = nullptr;
-    hipStream_t st = fm3d_internal_stream(c);
-    VCHK(c, hipSetDevice(fm3d_internal_device(c)));
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
     int nCU = 0;
-    VCHK(c, hipDeviceGetAttribute(&nCU, hipDeviceAttributeMultiprocessorCount, fm3d_internal_device(c)));
+    HIPCHK(c, hipDeviceGetAttribute(&nCU, hipDeviceAttributeMultiprocessorCount, c->device));
     const int Mpad = fm3d::verify_pad(M);
     Carver cv;
     const size_t oK1 = cv.take((size_t)n1 * sizeof(fm3d_point2f)), oK2 = cv.take((size_t)n2 * sizeof(fm3d_point2f));
@@ -184,31 +166,29 @@ int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm
     const size_t oFlag = cv.take((size_t)M * sizeof(int)), oMask = cv.take((size_t)M);
     const size_t oOut = cv.take((size_t)(M + 1) * sizeof(fm3d_dmatch)), oN = cv.take(sizeof(int));
     const size_t oTmp = cv.take(fm3d::scan_tmp_bytes(M));
-    VCHK(c, hipMalloc((void**)&pool, cv.off));
-    VCHK(c, hipMemcpyAsync(pool + oK1, kpts1, (size_t)n1 * sizeof(fm3d_point2f), hipMemcpyHostToDevice, st));
-    VCHK(c, hipMemcpyAsync(pool + oK2, kpts2, (size_t)n2 * sizeof(fm3d_point2f), hipMemcpyHostToDevice, st));
-    VCHK(c, hipMemcpyAsync(pool + oM, matches, (size_t)M * sizeof(fm3d_dmatch), hipMemcpyHostToDevice, st));
+    DevBuf buf;
+    HIPCHK(c, buf.ensure(cv.off));
+    char* const pool = buf.as<char>();
+    HIPCHK(c, hipMemcpyAsync(pool + oK1, kpts1, (size_t)n1 * sizeof(fm3d_point2f), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(pool + oK2, kpts2, (size_t)n2 * sizeof(fm3d_point2f), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(pool + oM, matches, (size_t)M * sizeof(fm3d_dmatch), hipMemcpyHostToDevice, st));
     fm3d::launch_verify(cam, (const fm3d_point2f*)(pool + oK1), (const fm3d_point2f*)(pool + oK2),
                         (const fm3d_dmatch*)(pool + oM), M, H, seed, tau2, nCU, (double*)(pool + oXY),
                         (double*)(pool + oMod), (int*)(pool + oCnt), (int*)(pool + oBest), (double*)(pool + oE),
                         (int*)(pool + oFlag), (uint8_t*)(pool + oMask), st);
     fm3d::launch_compact_dmatch((const fm3d_dmatch*)(pool + oM), (const int*)(pool + oFlag), M,
                                 (fm3d_dmatch*)(pool + oOut), (int*)(pool + oN), pool + oTmp, st);
-    VCHK(c, hipGetLastError());
+    HIPCHK(c, hipGetLastError());
     int n = 0;
-    VCHK(c, hipMemcpyAsync(&n, pool + oN, sizeof(int), hipMemcpyDeviceToHost, st));
-    VCHK(c, hipMemcpyAsync(best, pool + oBest, sizeof(int), hipMemcpyDeviceToHost, st));
-    VCHK(c, hipMemcpyAsync(E, pool + oE, 9 * sizeof(double), hipMemcpyDeviceToHost, st));
-    VCHK(c, hipMemcpyAsync(inlierMask, pool + oMask, (size_t)M, hipMemcpyDeviceToHost, st));
-    if (counts) VCHK(c, hipMemcpyAsync(counts, pool + oCnt, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (models) VCHK(c, hipMemcpyAsync(models, pool + oMod, (size_t)H * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
-    VCHK(c, hipStreamSynchronize(st));
-    if (n < 0 || n > M) {
-        hipFree(pool);
-        return fm3d_internal_fail(c, FM3D_ERR_HIP, "verify: inlier count out of range");
-    }
-    if (n) VCHK(c, hipMemcpy(inliers, pool + oOut, (size_t)n * sizeof(fm3d_dmatch), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpyAsync(&n, pool + oN, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(best, pool + oBest, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(E, pool + oE, 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(inlierMask, pool + oMask, (size_t)M, hipMemcpyDeviceToHost, st));
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts, pool + oCnt, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (models) HIPCHK(c, hipMemcpyAsync(models, pool + oMod, (size_t)H * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (n < 0 || n > M) return fail(c, FM3D_ERR_HIP, "verify: inlier count out of range");
+    if (n) HIPCHK(c, hipMemcpy(inliers, pool + oOut, (size_t)n * sizeof(fm3d_dmatch), hipMemcpyDeviceToHost));
     *nInliers = n;
-    hipFree(pool);
     return FM3D_OK;
 }

@@ -1,6 +1,6 @@
-// san_host.cpp -- the host algebra of libfm3d (csrc/fm3d_host.cpp: setg12, Rodrigues both ways,
-// Matx44d::inv, gravity, patch size) compiled with host-side AddressSanitizer +
-// UndefinedBehaviorSanitizer (hipcc -Xarch_host -fsanitize=...) and driven through the C ABI's
+// san_host.cpp -- the host algebra of libfm3d (csrc/fm3d_algebra.cpp: setg12, Rodrigues both ways,
+// Matx44d::inv, gravity, patch size) compiled with AddressSanitizer +
+// UndefinedBehaviorSanitizer (g++ -fsanitize=...) and driven through the C ABI's
 // context-free entry points (no GPU needed), including near-identity and half-turn rotations and
 // a singular IMU rotation.  Run by tests/test_sanitizers.py.
 #include <cmath>

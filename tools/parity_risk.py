@@ -6,7 +6,7 @@ with the libm oracle (STRICT) under input perturbations that an unpinned OpenCV 
 plausibly introduce, and compared with the unperturbed run:
 
   * R2 from an SVD polar factor (numpy SVD: OpenCV's cvRodrigues2 orthonormalises R by
-    cvSVD, U V^T) instead of the three Newton polar steps of fm3d_host.cpp rodrigues_m2v;
+    cvSVD, U V^T) instead of the three Newton polar steps of fm3d_algebra.cpp rodrigues_m2v;
   * t2 moved by one ulp (each component up; each component down);
   * fx moved by one ulp (undistortion of the neighbourhood pixels and the camera-2
     projection: the inputs of every bilinear sample coordinate);
@@ -43,7 +43,7 @@ import oracle as orc  # noqa: E402  (checker)
 
 def m2v_no_polar(R):
     """cvRodrigues2 matrix -> vector after the orthonormalisation (OpenCV 2.4 calibration.cpp),
-    the same branch structure as fm3d_host.cpp rodrigues_m2v."""
+    the same branch structure as fm3d_algebra.cpp rodrigues_m2v."""
     rx, ry, rz = R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]
     s = math.sqrt((rx * rx + ry * ry + rz * rz) * 0.25)
     c = (R[0, 0] + R[1, 1] + R[2, 2] - 1) * 0.5
