@@ -49,6 +49,7 @@ EXPORTS = (
     "fm3d_match_mutual", "fm3d_match_mutual_guided", "fm3d_math_probe",
     "fm3d_verify_matches", "fm3d_ransac_sample", "fm3d_epipolar_from8", "fm3d_epipolar_null8", "fm3d_epipolar_count",
     "fm3d_pose_from_epipolar",
+    "fm3d_verify_matches_refined", "fm3d_epipolar_normal45", "fm3d_epipolar_refit",
 )
 
 # include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
@@ -781,16 +782,25 @@ class SingleCameraTriangulator:
         self.ctx.check(lib().fm3d_epipolar_lines(self.ctx.handle, _vp(k1), k1.shape[0], _vp(out)))
         return out
 
-    def verifyMatches(self, kp1, kp2, matches, max_px, hypotheses: int = 1024, seed: int = 0, debug: bool = False):
+    def verifyMatches(self, kp1, kp2, matches, max_px, hypotheses: int = 1024, seed: int = 0, debug: bool = False,
+                      refine: int = 0):
         """fm3d_verify_matches: a RANSAC fit of the essential matrix to the matches,
         `hypotheses` eight-point models scored against every match within max_px pixels -> (E (3, 3),
         mask (K,) bool, inliers (DMATCH, input order), best); with debug also counts (H,) int32 (-1 for an
         invalid hypothesis) and models (H, 3, 3).  No valid model: a zero E, no inliers, best -1.  Uses
-        the camera of the context's settings, not g12."""
+        the camera of the context's settings, not g12.
+        refine (0 .. 16, fm3d_verify_matches_refined): that many rounds of a least-squares refit of the
+        best model on its own inliers, each adopted iff valid and no worse in count; E, mask and inliers
+        are the final model's.  With refine > 0 and debug three more: roundCounts (refine + 1,) int32
+        (c_0, then each round's count: -1 an invalid refit, -2 a round not run), roundModels
+        (refine, 3, 3) and the number of rounds adopted."""
         _check_max_px(max_px)
         H = int(hypotheses)
         if H < 1:
             raise Fm3dError(ERR_INVALID, "hypotheses must be >= 1")
+        R = int(refine)
+        if not 0 <= R <= 16:
+            raise Fm3dError(ERR_INVALID, "refine must be in 0 .. 16")
         k1 = np.ascontiguousarray(kp1, dtype=np.float32).reshape(-1, 2)
         k2 = np.ascontiguousarray(kp2, dtype=np.float32).reshape(-1, 2)
         m = np.ascontiguousarray(matches, dtype=DMATCH)
@@ -801,12 +811,24 @@ class SingleCameraTriangulator:
         n, best = ctypes.c_int(0), ctypes.c_int(-1)
         counts = np.zeros(H, dtype=np.int32) if debug else None
         models = np.zeros((H, 9)) if debug else None
-        self.ctx.check(lib().fm3d_verify_matches(
-            self.ctx.handle, _vp(k1), k1.shape[0], _vp(k2), k2.shape[0], _vp(m), K, H, ctypes.c_double(float(max_px)),
-            ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(E), _ptr(mask, ctypes.c_uint8), _vp(out),
-            ctypes.byref(n), ctypes.byref(best), _vp(counts), _vp(models)))
+        head = (self.ctx.handle, _vp(k1), k1.shape[0], _vp(k2), k2.shape[0], _vp(m), K, H, ctypes.c_double(float(max_px)),
+                ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF))
+        tail = (_ptr(E), _ptr(mask, ctypes.c_uint8), _vp(out), ctypes.byref(n), ctypes.byref(best), _vp(counts),
+                _vp(models))
+        if R == 0:
+            self.ctx.check(lib().fm3d_verify_matches(*head, *tail))
+        else:
+            rc = np.zeros(R + 1, dtype=np.int32) if debug else None
+            rm = np.zeros((R, 9)) if debug else None
+            adopted = ctypes.c_int(0)
+            self.ctx.check(lib().fm3d_verify_matches_refined(*head, ctypes.c_int(R), *tail, _vp(rc), _vp(rm),
+                                                             ctypes.byref(adopted)))
         res = (E.reshape(3, 3), mask[:K].astype(bool), out[:n.value].copy(), best.value)
-        return res + (counts, models.reshape(H, 3, 3)) if debug else res
+        if debug:
+            res += (counts, models.reshape(H, 3, 3))
+            if R:
+                res += (rc, rm.reshape(R, 3, 3), adopted.value)
+        return res
 
     def plane_to_image2(self, X, n):
         """fm3d_plane_to_image2 (device kernel): extractPixelsContour(X) and the level-0 projection of
@@ -1338,6 +1360,34 @@ def epipolar_count(E, x1, x2, tau: float):
     if rc < 0:
         _check(rc)
     return rc, mask[:a.shape[0]].astype(bool)
+
+
+def epipolar_normal45(E, x1, x2, tau: float):
+    """fm3d_epipolar_normal45: the 45 entries (r <= c, row by row) of the sum of a a^T over the pairs the
+    model accepts at tau, in the refit's summation order (host only) -> (N45 (45,), pairs in)."""
+    a, b = _pairs(x1), _pairs(x2)
+    if a.shape != b.shape:
+        raise ValueError("x1 and x2 differ in length")
+    N = np.zeros(45)
+    rc = lib().fm3d_epipolar_normal45(_ptr(np.ascontiguousarray(E, dtype=np.float64).ravel()), _ptr(a), _ptr(b),
+                                      a.shape[0], ctypes.c_double(float(tau)), _ptr(N))
+    if rc < 0:
+        _check(rc)
+    return N, rc
+
+
+def epipolar_refit(E, x1, x2, tau: float):
+    """fm3d_epipolar_refit: the least-squares essential matrix of the pairs the model E accepts at tau
+    (host only) -> (E' (3, 3), valid); an invalid refit is zero."""
+    a, b = _pairs(x1), _pairs(x2)
+    if a.shape != b.shape:
+        raise ValueError("x1 and x2 differ in length")
+    out = np.zeros(9)
+    rc = lib().fm3d_epipolar_refit(_ptr(np.ascontiguousarray(E, dtype=np.float64).ravel()), _ptr(a), _ptr(b),
+                                   a.shape[0], ctypes.c_double(float(tau)), _ptr(out))
+    if rc < 0:
+        _check(rc)
+    return out.reshape(3, 3), rc == 0
 
 
 def pose_from_epipolar(E, x1, x2, baseline: float = 1.0):

@@ -334,7 +334,15 @@ int verify_pad(int M);                    // M rounded up to whole tiles
 // M >= 8, 1 <= H <= kVerifyMaxHyps, every match index inside its keypoint array.
 void launch_verify(const Camera& cam, const fm3d_point2f* kp1, const fm3d_point2f* kp2, const fm3d_dmatch* matches,
                    int M, int H, unsigned long long seed, double tau2, int nCU, double* xy, double* models, int* count,
-                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s);
+                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s, bool withMask = true);
+// The refinement after launch_verify(..., withMask = false): `rounds` (1 .. 16) refits of E on its own
+// inliers, each adopted iff valid and no worse in count, all queued on s without a host sync, then the
+// mask of the final E.  work: verify_refine_bytes(M, rounds), 8-byte aligned; the three outputs point
+// into it: roundCounts (rounds + 1 ints), roundModels (rounds x 9), adopted (1 int).
+size_t verify_refine_bytes(int M, int rounds);
+void launch_verify_refine(int M, int rounds, double tau2, const double* xy, const int* count, const int* best,
+                          double* E, void* work, int* flag, uint8_t* mask, int** roundCounts, double** roundModels,
+                          int** adopted, hipStream_t s);
 
 // ---------------- triangulation ----------------
 struct TriParams {

@@ -1,5 +1,6 @@
 // fm3d_verify.cpp -- geometric verification, the host side: fm3d_verify_matches'
-// orchestration and the context-free algebra (sampler, eight-point model, count, pose from E).
+// orchestration (with the refinement rounds of fm3d_verify_matches_refined) and the context-free
+// algebra (sampler, eight-point model, count, normal matrix and refit, pose from E).
 // The arithmetic is include/fm3d_epi8.h's; the kernels are fm3d_verify.hip's.
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "fm3d.h"
 #include "fm3d_ctx.h"
@@ -123,11 +125,75 @@ int fm3d_pose_from_epipolar(const double E[9], const double* x1, const double* x
     return 0;
 }
 
+// The 45 sums of a_i a_i^T over the pairs E accepts, in the contract's order: per tile of 1,024 slots
+// the leaves (slot k * 256 + t belongs to leaf t), a balanced tree over the 256 leaves, then the tiles
+// in order from +0.0.  Returns the number of pairs in.
+static int normal45(const double E[9], const double* x1, const double* x2, int n, double tau2, double N45[45]) {
+    using namespace fm3d_epi8;
+    for (int j = 0; j < kPairs; j++) N45[j] = 0.;
+    std::vector<double> a((size_t)kRefitTile * 9);
+    std::vector<uint8_t> in(kRefitTile);
+    double leaf[kRefitLanes];
+    int cnt = 0;
+    for (int base = 0; base < n; base += kRefitTile) {
+        for (int s = 0; s < kRefitTile; s++) {
+            const int i = base + s;
+            double r[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
+            in[s] = 0;
+            if (i < n) {
+                in[s] = inlier(E, x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1], tau2) ? 1 : 0;
+                row9(x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1], r);
+            }
+            cnt += in[s];
+            for (int k = 0; k < 9; k++) a[(size_t)s * 9 + k] = r[k];
+        }
+        int j = 0;
+        for (int r = 0; r < 9; r++)
+            for (int c = r; c < 9; c++, j++) {
+                for (int t = 0; t < kRefitLanes; t++) {
+                    double v[4];
+                    for (int k = 0; k < 4; k++) {
+                        const int s = k * kRefitLanes + t;
+                        const double(&as)[9] = *reinterpret_cast<const double(*)[9]>(&a[(size_t)s * 9]);
+                        v[k] = slot(in[s] != 0, as, r, c);
+                    }
+                    leaf[t] = leaf4(v[0], v[1], v[2], v[3]);
+                }
+                for (int w = kRefitLanes / 2; w >= 1; w >>= 1)
+                    for (int i = 0; i < w; i++) leaf[i] = leaf[2 * i] + leaf[2 * i + 1];
+                N45[j] = N45[j] + leaf[0];
+            }
+    }
+    return cnt;
+}
+
+int fm3d_epipolar_normal45(const double E[9], const double* x1, const double* x2, int n, double tau, double N45[45]) {
+    if (!E || !N45 || n < 0 || ((!x1 || !x2) && n)) return FM3D_ERR_INVALID;
+    return normal45(E, x1, x2, n, tau * tau, N45);
+}
+
+int fm3d_epipolar_refit(const double E[9], const double* x1, const double* x2, int n, double tau, double Eout[9]) {
+    if (!E || !Eout || n < 0 || ((!x1 || !x2) && n)) return FM3D_ERR_INVALID;
+    double N45[45];
+    normal45(E, x1, x2, n, tau * tau, N45);
+    fm3d_epi8::Mat99 S, V;
+    return fm3d_epi8::refit45(N45, S, V, Eout) ? 0 : 1;
+}
+
 int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm3d_point2f* kpts2, int n2,
                         const fm3d_dmatch* matches, int nMatches, int hypotheses, double maxPx, uint64_t seed,
                         double E[9], uint8_t* inlierMask, fm3d_dmatch* inliers, int* nInliers, int* best,
                         int32_t* counts, double* models) {
-    const int M = nMatches, H = hypotheses;
+    return fm3d_verify_matches_refined(c, kpts1, n1, kpts2, n2, matches, nMatches, hypotheses, maxPx, seed, 0, E,
+                                       inlierMask, inliers, nInliers, best, counts, models, nullptr, nullptr, nullptr);
+}
+
+int fm3d_verify_matches_refined(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm3d_point2f* kpts2, int n2,
+                                const fm3d_dmatch* matches, int nMatches, int hypotheses, double maxPx, uint64_t seed,
+                                int refineIters, double E[9], uint8_t* inlierMask, fm3d_dmatch* inliers, int* nInliers,
+                                int* best, int32_t* counts, double* models, int32_t* roundCounts, double* roundModels,
+                                int* roundsAdopted) {
+    const int M = nMatches, H = hypotheses, R = refineIters;
     if (!c || !E || !nInliers || !best || n1 < 0 || n2 < 0 || M < 0 || (!kpts1 && n1) || (!kpts2 && n2) ||
         ((!matches || !inlierMask || !inliers) && M))
         return fail(c, FM3D_ERR_INVALID, "null argument");
@@ -136,12 +202,20 @@ int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm
     for (int i = 0; i < M; i++)
         if (matches[i].queryIdx < 0 || matches[i].queryIdx >= n1 || matches[i].trainIdx < 0 || matches[i].trainIdx >= n2)
             return fail(c, FM3D_ERR_INVALID, "match index out of range");
+    if (R < 0 || R > fm3d_epi8::kRefitMaxIters) return fail(c, FM3D_ERR_INVALID, "refineIters must be in 0 .. 16");
     if (H > fm3d::kVerifyMaxHyps) return fail(c, FM3D_ERR_UNSUPPORTED, "more than 2^20 hypotheses");
 
     for (int k = 0; k < 9; k++) E[k] = 0.;
     *nInliers = 0;
     *best = -1;
     if (M) std::memset(inlierMask, 0, (size_t)M);
+    // until a round runs: no best model gives c_0 = -1, and every round -2 and a zero candidate
+    if (roundCounts) {
+        roundCounts[0] = -1;
+        for (int r = 0; r < R; r++) roundCounts[1 + r] = -2;
+    }
+    if (roundModels && R) std::memset(roundModels, 0, (size_t)R * 9 * sizeof(double));
+    if (roundsAdopted) *roundsAdopted = 0;
     if (M < 8) {  // no sample exists: every hypothesis is invalid
         if (counts)
             for (int h = 0; h < H; h++) counts[h] = -1;
@@ -166,6 +240,7 @@ int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm
     const size_t oFlag = cv.take((size_t)M * sizeof(int)), oMask = cv.take((size_t)M);
     const size_t oOut = cv.take((size_t)(M + 1) * sizeof(fm3d_dmatch)), oN = cv.take(sizeof(int));
     const size_t oTmp = cv.take(fm3d::scan_tmp_bytes(M));
+    const size_t oRef = R ? cv.take(fm3d::verify_refine_bytes(M, R)) : 0;
     DevBuf buf;
     HIPCHK(c, buf.ensure(cv.off));
     char* const pool = buf.as<char>();
@@ -175,7 +250,13 @@ int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm
     fm3d::launch_verify(cam, (const fm3d_point2f*)(pool + oK1), (const fm3d_point2f*)(pool + oK2),
                         (const fm3d_dmatch*)(pool + oM), M, H, seed, tau2, nCU, (double*)(pool + oXY),
                         (double*)(pool + oMod), (int*)(pool + oCnt), (int*)(pool + oBest), (double*)(pool + oE),
-                        (int*)(pool + oFlag), (uint8_t*)(pool + oMask), st);
+                        (int*)(pool + oFlag), (uint8_t*)(pool + oMask), st, R == 0);
+    int *dRoundCounts = nullptr, *dAdopted = nullptr;
+    double* dRoundModels = nullptr;
+    if (R)  // every round queued now: the call keeps its one sync at the end
+        fm3d::launch_verify_refine(M, R, tau2, (const double*)(pool + oXY), (const int*)(pool + oCnt),
+                                   (const int*)(pool + oBest), (double*)(pool + oE), pool + oRef, (int*)(pool + oFlag),
+                                   (uint8_t*)(pool + oMask), &dRoundCounts, &dRoundModels, &dAdopted, st);
     fm3d::launch_compact_dmatch((const fm3d_dmatch*)(pool + oM), (const int*)(pool + oFlag), M,
                                 (fm3d_dmatch*)(pool + oOut), (int*)(pool + oN), pool + oTmp, st);
     HIPCHK(c, hipGetLastError());
@@ -186,9 +267,17 @@ int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm
     HIPCHK(c, hipMemcpyAsync(inlierMask, pool + oMask, (size_t)M, hipMemcpyDeviceToHost, st));
     if (counts) HIPCHK(c, hipMemcpyAsync(counts, pool + oCnt, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, st));
     if (models) HIPCHK(c, hipMemcpyAsync(models, pool + oMod, (size_t)H * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (R) {
+        if (roundCounts)
+            HIPCHK(c, hipMemcpyAsync(roundCounts, dRoundCounts, (size_t)(R + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (roundModels)
+            HIPCHK(c, hipMemcpyAsync(roundModels, dRoundModels, (size_t)R * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (roundsAdopted) HIPCHK(c, hipMemcpyAsync(roundsAdopted, dAdopted, sizeof(int), hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(c, hipStreamSynchronize(st));
     if (n < 0 || n > M) return fail(c, FM3D_ERR_HIP, "verify: inlier count out of range");
     if (n) HIPCHK(c, hipMemcpy(inliers, pool + oOut, (size_t)n * sizeof(fm3d_dmatch), hipMemcpyDeviceToHost));
     *nInliers = n;
+    if (R == 0 && roundCounts && *best >= 0) roundCounts[0] = n;  // c_0: the best model's count
     return FM3D_OK;
 }

@@ -1,7 +1,8 @@
 // fm3d_verify.hip -- geometric verification of matches: a RANSAC fit of the
-// essential matrix, every hypothesis scored against every match.  The arithmetic is
-// include/fm3d_epi8.h's (shared with the host entry points and restated in tests/verify_pyref.py);
-// the kernels only distribute it.
+// essential matrix, every hypothesis scored against every match, and the rounds of a least-squares
+// refit of the best model on its inliers.  The arithmetic is include/fm3d_epi8.h's (shared with the
+// host entry points and restated in tests/verify_pyref.py and tests/verify_refit_pyref.py); the
+// kernels only distribute it.
 #include <hip/hip_runtime.h>
 
 #include "fm3d_epi8.h"
@@ -162,13 +163,205 @@ __global__ __launch_bounds__(256) void verify_mask_kernel(const double* __restri
     mask[i] = in ? 1 : 0;
 }
 
+// ---------------- refinement: the refit on the inliers, round by round ----------------
+// st: the rounds' state on the device.  Every kernel of a round tests st[kStDone] first.
+enum { kStDone = 0, kStCount = 1, kStValid = 2, kStCand = 3, kStAdopted = 4, kStWords = 8 };
+
+static_assert(kScoreThreads == fm3d_epi8::kRefitLanes && kVerifyTile == fm3d_epi8::kRefitTile,
+              "the normal matrix is summed over the scoring kernel's tile");
+
+// c_0 and the flags: no best model leaves every round undone
+__global__ __launch_bounds__(64) void verify_refine_init_kernel(const int* __restrict__ best,
+                                                                const int* __restrict__ count, int rounds,
+                                                                int* __restrict__ st, int* __restrict__ roundCounts,
+                                                                double* __restrict__ roundModels) {
+    const int tid = threadIdx.x;
+    const int b = *best;
+    const int c0 = b >= 0 ? count[b] : -1;
+    if (tid == 0) {
+        st[kStDone] = b < 0;
+        st[kStCount] = c0;
+        st[kStValid] = 0;
+        st[kStCand] = -1;
+        st[kStAdopted] = 0;
+        roundCounts[0] = c0;
+    }
+    for (int r = tid; r < rounds; r += 64) roundCounts[1 + r] = -2;
+    for (int k = tid; k < rounds * 9; k += 64) roundModels[k] = 0.;
+}
+
+// Workgroup bx: the 45 sums of tile bx under the current model.  A lane holds the four slots
+// k * 256 + tid, evaluates the predicate itself and forms leaf4 of their products; the wave's 64
+// leaves go through an xor butterfly (strides 1 .. 32: the balanced tree's bits in every lane, IEEE
+// addition being commutative), the four waves through LDS as (w0 + w1) + (w2 + w3).
+__global__ __launch_bounds__(kScoreThreads) void verify_normal_kernel(const double* __restrict__ xy, int Mpad,
+                                                                      const double* __restrict__ Ecur, double tau2,
+                                                                      const int* __restrict__ st,
+                                                                      double* __restrict__ partial) {
+    __shared__ double sW[kScoreThreads / 64][fm3d_epi8::kPairs];
+    if (st[kStDone]) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double E[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) E[k] = Ecur[k];
+    static_assert(kScorePer == 4, "leaf4 adds a lane's four slots");
+    double a[kScorePer][9];
+    bool in[kScorePer];
+#pragma unroll
+    for (int k = 0; k < kScorePer; k++) {
+        const size_t i = (size_t)blockIdx.x * kVerifyTile + k * kScoreThreads + tid;  // < Mpad
+        const double x1 = xy[i], y1 = xy[(size_t)Mpad + i], x2 = xy[(size_t)2 * Mpad + i], y2 = xy[(size_t)3 * Mpad + i];
+        in[k] = fm3d_epi8::inlier(E, x1, y1, x2, y2, tau2);
+        fm3d_epi8::row9(x1, y1, x2, y2, a[k]);
+    }
+    int j = 0;
+#pragma unroll
+    for (int r = 0; r < 9; r++)
+#pragma unroll
+        for (int c = r; c < 9; c++, j++) {
+            double s = fm3d_epi8::leaf4(fm3d_epi8::slot(in[0], a[0], r, c), fm3d_epi8::slot(in[1], a[1], r, c),
+                                        fm3d_epi8::slot(in[2], a[2], r, c), fm3d_epi8::slot(in[3], a[3], r, c));
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) s = s + __shfl_xor(s, o);
+            if (lane == 0) sW[wave][j] = s;
+        }
+    __syncthreads();
+    if (tid < fm3d_epi8::kPairs)
+        partial[(size_t)blockIdx.x * fm3d_epi8::kPairs + tid] = (sW[0][tid] + sW[1][tid]) + (sW[2][tid] + sW[3][tid]);
+}
+
+// S and V of the solve in LDS: the rotations index them at run time
+struct LdsMat99 {
+    double* p;
+    __device__ double& operator()(int r, int c) { return p[r * 9 + c]; }
+};
+
+// the solve's rows over the lanes of its one wave: row k on lane k (the lanes from 9 on only follow)
+struct WaveTeam {
+    int lane;
+    __device__ int first() const { return lane; }
+    __device__ int step() const { return 64; }
+    __device__ void sync() const { __syncthreads(); }
+};
+
+// One workgroup of one wave: 45 threads add the tile partials in tile order from +0.0; every lane runs
+// the Jacobi iteration on the S and V in LDS, lane k updating row k of a rotation; thread 0 projects.
+// cand: E' (zero when invalid); st: the valid flag and the candidate's count, 0 for the count kernel
+// to add to, -1 when there is nothing to count.
+__global__ __launch_bounds__(64) void verify_solve_kernel(const double* __restrict__ partial, int tiles,
+                                                          int* __restrict__ st, double* __restrict__ cand) {
+    __shared__ double sN[fm3d_epi8::kPairs], sS[81], sV[81], sE[9];
+    __shared__ int sOk;
+    const int tid = threadIdx.x;
+    if (st[kStDone]) return;
+    if (tid < fm3d_epi8::kPairs) {
+        double s = 0.;
+        for (int t = 0; t < tiles; t++) s = s + partial[(size_t)t * fm3d_epi8::kPairs + tid];
+        sN[tid] = s;
+    }
+    __syncthreads();
+    LdsMat99 S{sS}, V{sV};
+    if (tid == 0) sOk = fm3d_epi8::refit_load(sN, S) ? 1 : 0;
+    __syncthreads();
+    const bool ok = sOk != 0;  // the same in every lane: the barriers below are met by all or none
+    if (ok) fm3d_epi8::jacobi_null9(S, V, sE, WaveTeam{tid});
+    if (tid == 0) {
+        double E[9];
+        const bool valid = fm3d_epi8::refit_project(ok, sE, E);
+#pragma unroll
+        for (int k = 0; k < 9; k++) cand[k] = E[k];
+        st[kStValid] = valid ? 1 : 0;
+        st[kStCand] = valid ? 0 : -1;
+    }
+}
+
+// c' of a valid E': verify_score_kernel's count for one model, behind the rounds' flags (integers:
+// the atomicAdd per workgroup is exact in any order)
+__global__ __launch_bounds__(kScoreThreads) void verify_count_kernel(const double* __restrict__ xy, int Mpad,
+                                                                     const double* __restrict__ cand, double tau2,
+                                                                     int* __restrict__ st) {
+    __shared__ int sCnt[kScoreThreads / 64];
+    if (st[kStDone] || !st[kStValid]) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double E[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) E[k] = cand[k];
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < kScorePer; k++) {
+        const size_t i = (size_t)blockIdx.x * kVerifyTile + k * kScoreThreads + tid;  // < Mpad
+        c += __popcll(__ballot(
+            fm3d_epi8::inlier(E, xy[i], xy[(size_t)Mpad + i], xy[(size_t)2 * Mpad + i], xy[(size_t)3 * Mpad + i], tau2)));
+    }
+    if (lane == 0) sCnt[wave] = c;
+    __syncthreads();
+    if (tid == 0) {
+        const int n = (sCnt[0] + sCnt[1]) + (sCnt[2] + sCnt[3]);
+        if (n) atomicAdd(&st[kStCand], n);
+    }
+}
+
+// The rule of round r: adopt E' iff it is valid and keeps at least as many matches; otherwise the
+// current model is final and every later round is skipped.
+__global__ __launch_bounds__(64) void verify_adopt_kernel(int r, int* __restrict__ st, const double* __restrict__ cand,
+                                                          double* __restrict__ Ecur, int* __restrict__ roundCounts,
+                                                          double* __restrict__ roundModels) {
+    const int tid = threadIdx.x;
+    if (st[kStDone]) return;
+    const int valid = st[kStValid], cc = st[kStCand], cur = st[kStCount];
+    const bool adopt = valid && cc >= cur;
+    __syncthreads();  // every thread has read the state before thread 0 changes it
+    if (tid < 9) {
+        const double e = cand[tid];
+        roundModels[r * 9 + tid] = e;
+        if (adopt) Ecur[tid] = e;
+    }
+    if (tid == 0) {
+        roundCounts[1 + r] = cc;
+        if (adopt) {
+            st[kStCount] = cc;
+            st[kStAdopted] = st[kStAdopted] + 1;
+        } else {
+            st[kStDone] = 1;
+        }
+    }
+}
+
 }  // namespace
+
+size_t verify_refine_bytes(int M, int rounds) {
+    const size_t tiles = (size_t)verify_pad(M) / kVerifyTile;
+    return tiles * fm3d_epi8::kPairs * sizeof(double) + 9 * sizeof(double) + (size_t)rounds * 9 * sizeof(double) +
+           (size_t)(kStWords + 1 + rounds) * sizeof(int);
+}
+
+void launch_verify_refine(int M, int rounds, double tau2, const double* xy, const int* count, const int* best,
+                          double* E, void* work, int* flag, uint8_t* mask, int** roundCounts, double** roundModels,
+                          int** adopted, hipStream_t s) {
+    const int Mpad = verify_pad(M), tiles = Mpad / kVerifyTile;
+    double* partial = (double*)work;
+    double* cand = partial + (size_t)tiles * fm3d_epi8::kPairs;
+    double* rm = cand + 9;
+    int* st = (int*)(rm + (size_t)rounds * 9);
+    int* rc = st + kStWords;
+    verify_refine_init_kernel<<<1, 64, 0, s>>>(best, count, rounds, st, rc, rm);
+    for (int r = 0; r < rounds; r++) {
+        verify_normal_kernel<<<tiles, kScoreThreads, 0, s>>>(xy, Mpad, E, tau2, st, partial);
+        verify_solve_kernel<<<1, 64, 0, s>>>(partial, tiles, st, cand);
+        verify_count_kernel<<<tiles, kScoreThreads, 0, s>>>(xy, Mpad, cand, tau2, st);
+        verify_adopt_kernel<<<1, 64, 0, s>>>(r, st, cand, E, rc, rm);
+    }
+    verify_mask_kernel<<<(M + 255) / 256, 256, 0, s>>>(xy, M, Mpad, best, E, tau2, flag, mask);
+    *roundCounts = rc;
+    *roundModels = rm;
+    *adopted = st + kStAdopted;
+}
 
 int verify_pad(int M) { return (int)(((long long)M + kVerifyTile - 1) / kVerifyTile * kVerifyTile); }
 
 void launch_verify(const Camera& cam, const fm3d_point2f* kp1, const fm3d_point2f* kp2, const fm3d_dmatch* matches,
                    int M, int H, unsigned long long seed, double tau2, int nCU, double* xy, double* models, int* count,
-                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s) {
+                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s, bool withMask) {
     const int Mpad = verify_pad(M);
     verify_coords_kernel<<<(Mpad + 255) / 256, 256, 0, s>>>(cam, kp1, kp2, matches, M, Mpad, xy);
     verify_hypothesis_kernel<<<(H + kHypThreads - 1) / kHypThreads, kHypThreads, 0, s>>>(xy, M, Mpad, H, seed, models,
@@ -181,7 +374,7 @@ void launch_verify(const Camera& cam, const fm3d_point2f* kp1, const fm3d_point2
         hc >>= 1;
     verify_score_kernel<<<dim3(tiles, (H + hc - 1) / hc), kScoreThreads, 0, s>>>(xy, Mpad, models, H, hc, tau2, count);
     verify_argmax_kernel<<<1, 256, 0, s>>>(count, models, H, best, E);
-    verify_mask_kernel<<<(M + 255) / 256, 256, 0, s>>>(xy, M, Mpad, best, E, tau2, flag, mask);
+    if (withMask) verify_mask_kernel<<<(M + 255) / 256, 256, 0, s>>>(xy, M, Mpad, best, E, tau2, flag, mask);
 }
 
 }  // namespace fm3d

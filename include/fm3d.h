@@ -324,6 +324,33 @@ int fm3d_verify_matches(fm3d_ctx *ctx, const fm3d_point2f *kpts1, int n1, const 
                         const fm3d_dmatch *matches, int nMatches, int hypotheses, double maxPx, uint64_t seed,
                         double E[9], uint8_t *inlierMask, fm3d_dmatch *inliers, int *nInliers, int *best,
                         int32_t *counts, double *models);
+/* fm3d_verify_matches with local optimisation: after the RANSAC, refineIters rounds (0 .. 16) of a
+   least-squares refit of the model on its own inliers, all on the device.  With E_0 the best model and
+   c_0 its count, round r = 0 .. refineIters-1 fits E' = fm3d_epipolar_refit(E_r, all matches, tau),
+   counts c' = the matches E' accepts, and adopts (E_{r+1}, c_{r+1}) = (E', c') iff E' is valid and
+   c' >= c_r; otherwise E_r is final and no later round runs.  E, inlierMask, inliers are the final
+   model's; *best stays the RANSAC's index.  Optional outputs (may be NULL): roundCounts
+   (refineIters + 1 int32: c_0, or -1 when *best == -1, then each round's c', -1 for an invalid E', -2
+   for a round that did not run), roundModels (refineIters x 9: each round's E', zero when invalid or
+   not run), *roundsAdopted (the rounds adopted).  refineIters == 0 is fm3d_verify_matches byte for
+   byte.  Results depend on the inputs and the seed alone (no floating-point atomics: the sums have a
+   fixed order).  FM3D_ERR_INVALID also for refineIters outside 0 .. 16. */
+int fm3d_verify_matches_refined(fm3d_ctx *ctx, const fm3d_point2f *kpts1, int n1, const fm3d_point2f *kpts2, int n2,
+                                const fm3d_dmatch *matches, int nMatches, int hypotheses, double maxPx, uint64_t seed,
+                                int refineIters, double E[9], uint8_t *inlierMask, fm3d_dmatch *inliers, int *nInliers,
+                                int *best, int32_t *counts, double *models, int32_t *roundCounts, double *roundModels,
+                                int *roundsAdopted);
+/* The refit's algebra on the host (no context), the code the kernels run.
+   fm3d_epipolar_normal45: N = sum of a a^T over the pairs E accepts at tau (fm3d_epipolar_count's
+   test), a = (x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1); N45: its 45 entries (r, c), r <= c, row by
+   row, summed in the order of DESIGN.md §3.1d (tiles of 1,024 pairs, a balanced tree inside a tile,
+   tiles in order).  Returns the number of pairs in.
+   fm3d_epipolar_refit: the eigenvector of N's smallest eigenvalue by a cyclic Jacobi iteration, then
+   singular values (1, 1, 0) as in fm3d_epipolar_from8; returns 1 and a zero Eout when invalid (fewer
+   than 8 pairs in, a non-finite entry of N or of the eigenvector, a projection that fails).
+   FM3D_ERR_INVALID: a null pointer, a negative n. */
+int fm3d_epipolar_normal45(const double E[9], const double *x1, const double *x2, int n, double tau, double N45[45]);
+int fm3d_epipolar_refit(const double E[9], const double *x1, const double *x2, int n, double tau, double Eout[9]);
 /* The stage's algebra on the host (no context, usable without a GPU), the same code the kernels run.
    fm3d_ransac_sample: the eight distinct indices in [0, M) of hypothesis h; returns 1 (idx partly -1)
    when 64 draws give fewer, as every M < 8 does.

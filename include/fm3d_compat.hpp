@@ -297,6 +297,32 @@ public:
         }
         return best;
     }
+    // The same with local optimisation (fm3d_verify_matches_refined): refineIters rounds (0 .. 16) of
+    // a least-squares refit of the best model on its own inliers, each adopted iff valid and no worse
+    // in count; E and inliers are the final model's.  roundsAdopted (optional): the rounds adopted.
+    int verifyMatches(const std::vector<KeyPoint>& k1, const std::vector<KeyPoint>& k2,
+                      const std::vector<DMatch>& matches, double maxPx, int refineIters, std::vector<DMatch>& inliers,
+                      std::array<double, 9>& E, int hypotheses = 1024, uint64_t seed = 0,
+                      std::vector<bool>* inlierMask = nullptr, int* roundsAdopted = nullptr) {
+        std::vector<fm3d_point2f> a(k1.size()), b(k2.size());
+        for (size_t i = 0; i < k1.size(); i++) a[i] = fm3d_point2f{k1[i].pt.x, k1[i].pt.y};
+        for (size_t i = 0; i < k2.size(); i++) b[i] = fm3d_point2f{k2[i].pt.x, k2[i].pt.y};
+        const int K = (int)matches.size();
+        std::vector<uint8_t> mask(K > 0 ? K : 1);
+        std::vector<DMatch> kept(K > 0 ? K : 1);
+        int n = 0, best = -1;
+        check(d_.ctx(), fm3d_verify_matches_refined(d_.ctx(), a.data(), (int)a.size(), b.data(), (int)b.size(),
+                                                    matches.data(), K, hypotheses, maxPx, seed, refineIters, E.data(),
+                                                    mask.data(), kept.data(), &n, &best, nullptr, nullptr, nullptr,
+                                                    nullptr, roundsAdopted));
+        kept.resize(n);
+        inliers.swap(kept);
+        if (inlierMask) {
+            inlierMask->clear();
+            for (int i = 0; i < K; i++) inlierMask->push_back(mask[i] != 0);
+        }
+        return best;
+    }
     Device& device() const { return d_; }
 
 private:

@@ -6,7 +6,9 @@
  * by OpenCV 2.4's JacobiSVD (fm3d_cvsvd.h) and the Sampson test without a division.  Everything is
  * fp64 in the operand order written here, compiled without FMA contraction, so the host library, the
  * kernels of fm3d_verify.hip and the numpy restatement (tests/verify_pyref.py) give the same bits.
- * This header is the only place the arithmetic lives.
+ * The refit of a model on its own inliers follows: the 45 sums of the normal matrix in a fixed order,
+ * a cyclic Jacobi eigen-iteration on the symmetric 9 x 9 and the same projection
+ * (tests/verify_refit_pyref.py).  This header is the only place the arithmetic lives.
  */
 #ifndef FM3D_EPI8_H
 #define FM3D_EPI8_H
@@ -192,6 +194,159 @@ FM3D_CVSVD_HD bool inlier(const double E[9], double x1, double y1, double x2, do
     const double r = (x2 * l0 + y2 * l1) + l2;
     const double den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
     return (den > 0.) & (r * r <= tau2 * den);  // both evaluated: no branch per pair in the scoring loop
+}
+
+// ---------------- the refit on the inliers ("Refinement") ----------------
+
+constexpr int kPairs = 45;         // the entries (r, c), r <= c, of the symmetric 9 x 9, row by row
+constexpr int kRefitTile = 1024;   // slots of one summation tile (the scoring kernel's tile)
+constexpr int kRefitLanes = 256;   // leaves of a tile's tree: slot k * 256 + t belongs to leaf t
+constexpr int kJacobiSweeps = 30;
+constexpr int kRefitMaxIters = 16;
+
+// the coefficients of one pair: set_row's nine entries
+FM3D_CVSVD_HD void row9(double x1, double y1, double x2, double y2, double (&a)[9]) {
+    a[0] = x2 * x1;
+    a[1] = x2 * y1;
+    a[2] = x2;
+    a[3] = y2 * x1;
+    a[4] = y2 * y1;
+    a[5] = y2;
+    a[6] = x1;
+    a[7] = y1;
+    a[8] = 1.;
+}
+
+// a slot's value for the entry (r, c): a[r] * a[c] when the pair is in, +0.0 otherwise (a select, not
+// a product with 0: a NaN adds nothing)
+FM3D_CVSVD_HD double slot(bool in, const double (&a)[9], int r, int c) { return in ? a[r] * a[c] : 0.; }
+
+// a thread's leaf of a tile: the four slots k * 256 + t as (v0 + v1) + (v2 + v3)
+FM3D_CVSVD_HD double leaf4(double v0, double v1, double v2, double v3) { return (v0 + v1) + (v2 + v3); }
+
+// a symmetric 9 x 9 (and its eigenvectors) on the host; the solve kernel keeps its own in LDS
+struct Mat99 {
+    double a[81];
+    FM3D_CVSVD_HD double& operator()(int r, int c) { return a[r * 9 + c]; }
+};
+
+// how the rows of a rotation are shared out: one thread on the host; the solve kernel gives row k to
+// lane k and puts a barrier where one lane reads what another wrote
+struct OneThread {
+    FM3D_CVSVD_HD int first() const { return 0; }
+    FM3D_CVSVD_HD int step() const { return 1; }
+    FM3D_CVSVD_HD void sync() const {}
+};
+
+// The eigenvector of the smallest eigenvalue of the symmetric S (both triangles stored; destroyed)
+// by cyclic Jacobi rotations, V the accumulated rotations.  Pairs (p, q), p = 0..7, q = p+1..8; a pair
+// rotates iff |S[p][q]| > 10 DBL_EPSILON sqrt(S[p][p] S[q][q]) (false for a NaN):
+//   theta = (S[q][q] - S[p][p]) / (2 S[p][q]),  t = sign(theta) / (|theta| + sqrt(theta theta + 1)),
+//   c = 1 / sqrt(t t + 1),  s = t c,  h = t S[p][q];
+//   S[p][p] -= h, S[q][q] += h, S[p][q] = S[q][p] = 0;
+//   for k != p, q: (S[k][p], S[k][q]) = (c S[k][p] - s S[k][q], s S[k][p] + c S[k][q]), mirrored;
+//   for every k:   (V[k][p], V[k][q]) = (c V[k][p] - s V[k][q], s V[k][p] + c V[k][q]).
+// It stops after a sweep without a rotation, after 30 sweeps at most.  e: the column of V under the
+// smallest S[j][j], the lowest j on ties.  Only + - * / sqrt.  The rows k of one rotation do not
+// depend on each other, so `team` may spread them over threads that all run this function on the same
+// S, V and e: every thread takes the same branches, and an entry's value does not depend on who
+// computes it.
+template <typename Mat, typename Team>
+FM3D_CVSVD_HD void jacobi_null9(Mat& S, Mat& V, double* e, const Team& team) {
+    for (int r = team.first(); r < 9; r += team.step())
+        for (int c = 0; c < 9; c++) V(r, c) = r == c ? 1. : 0.;
+    team.sync();
+    for (int sweep = 0; sweep < kJacobiSweeps; sweep++) {
+        bool rotated = false;
+        for (int p = 0; p < 8; p++)
+            for (int q = p + 1; q < 9; q++) {
+                const double apq = S(p, q), app = S(p, p), aqq = S(q, q);
+                const double thr = (10. * DBL_EPSILON) * sqrt(app * aqq);
+                if (!(fabs(apq) > thr)) continue;
+                rotated = true;
+                const double theta = (aqq - app) / (2. * apq);
+                const double t = (theta < 0. ? -1. : 1.) / (fabs(theta) + sqrt(theta * theta + 1.));
+                const double c = 1. / sqrt(t * t + 1.);
+                const double s = t * c;
+                const double h = t * apq;
+                team.sync();  // every thread has read the three entries
+                if (team.first() == 0) {
+                    S(p, p) = app - h;
+                    S(q, q) = aqq + h;
+                    S(p, q) = 0.;
+                    S(q, p) = 0.;
+                }
+                for (int k = team.first(); k < 9; k += team.step()) {
+                    if (k != p && k != q) {
+                        const double akp = S(k, p), akq = S(k, q);
+                        const double np = c * akp - s * akq, nq = s * akp + c * akq;
+                        S(k, p) = np;
+                        S(p, k) = np;
+                        S(k, q) = nq;
+                        S(q, k) = nq;
+                    }
+                    const double vkp = V(k, p), vkq = V(k, q);
+                    V(k, p) = c * vkp - s * vkq;
+                    V(k, q) = s * vkp + c * vkq;
+                }
+                team.sync();
+            }
+        if (!rotated) break;
+    }
+    int m = 0;
+    double least = S(0, 0);
+    for (int j = 1; j < 9; j++) {
+        const double d = S(j, j);
+        if (d < least) {
+            least = d;
+            m = j;
+        }
+    }
+    for (int k = team.first(); k < 9; k += team.step()) e[k] = V(k, m);
+    team.sync();
+}
+
+// The normal matrix N45 (the 45 sums, r <= c row by row) into S; false when the refit is invalid from
+// the start: a non-finite entry, or fewer than 8 pairs in (N[8][8] is their count: a[8] = 1)
+template <typename Mat>
+FM3D_CVSVD_HD bool refit_load(const double* N45, Mat& S) {
+    bool ok = true;
+    int j = 0;
+    for (int r = 0; r < 9; r++)
+        for (int c = r; c < 9; c++) {
+            const double v = N45[j++];
+            ok = ok && fabs(v) <= DBL_MAX;
+            S(r, c) = v;
+            S(c, r) = v;
+        }
+    return ok && N45[kPairs - 1] >= 8.;
+}
+
+// E' from the eigenvector; invalid (false, a zero E): a non-finite entry of e or a projection that fails
+FM3D_CVSVD_HD bool refit_project(bool ok, const double* e, double E[9]) {
+    if (ok) {
+        double ev[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            ev[k] = e[k];
+            ok = ok && fabs(ev[k]) <= DBL_MAX;
+        }
+        ok = ok && project_essential(ev, E);
+    }
+    if (!ok) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) E[k] = 0.;
+    }
+    return ok;
+}
+
+// the refit from the normal matrix on one thread (S, V: workspace)
+template <typename Mat>
+FM3D_CVSVD_HD bool refit45(const double* N45, Mat& S, Mat& V, double E[9]) {
+    double e[9];
+    const bool ok = refit_load(N45, S);
+    if (ok) jacobi_null9(S, V, e, OneThread());
+    return refit_project(ok, e, E);
 }
 
 }  // namespace fm3d_epi8
