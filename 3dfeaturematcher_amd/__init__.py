@@ -50,6 +50,7 @@ EXPORTS = (
     "fm3d_verify_matches", "fm3d_ransac_sample", "fm3d_epipolar_from8", "fm3d_epipolar_null8", "fm3d_epipolar_count",
     "fm3d_pose_from_epipolar",
     "fm3d_verify_matches_refined", "fm3d_epipolar_normal45", "fm3d_epipolar_refit",
+    "fm3d_pipeline_run_verified", "fm3d_pipeline_run_dlt_verified",
 )
 
 # include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
@@ -161,6 +162,27 @@ class PipelineStats(ctypes.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "lm"}
         d["lm"] = self.lm.as_dict()
+        return d
+
+
+class VerifyOpts(ctypes.Structure):
+    """fm3d_verify_opts (fm3d_pipeline_run_verified / fm3d_pipeline_run_dlt_verified)."""
+    _fields_ = [("hypotheses", ctypes.c_int32), ("refineIters", ctypes.c_int32), ("maxPx", ctypes.c_double),
+                ("seed", ctypes.c_uint64), ("poseFromModel", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("baseline", ctypes.c_double)]
+
+
+class VerifyReport(ctypes.Structure):
+    """fm3d_verify_report."""
+    _fields_ = [("matches", ctypes.c_int32), ("verified", ctypes.c_int32), ("best", ctypes.c_int32),
+                ("roundsAdopted", ctypes.c_int32), ("poseInstalled", ctypes.c_int32), ("votes", ctypes.c_int32 * 4),
+                ("E", ctypes.c_double * 9), ("g12", ctypes.c_double * 16), ("verify_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["votes"] = np.array(self.votes, dtype=np.int32)
+        d["E"] = np.array(self.E, dtype=np.float64).reshape(3, 3)
+        d["g12"] = np.array(self.g12, dtype=np.float64).reshape(4, 4)
         return d
 
 
@@ -1093,6 +1115,50 @@ class Pipeline:
         st = PipelineStats()
         self.ctx.check(lib().fm3d_pipeline_run_dlt(self.ctx.handle, ctypes.byref(n), ctypes.byref(st)))
         return n.value, st.as_dict()
+
+    @staticmethod
+    def _verify_opts(max_px, hypotheses, seed, refine, pose_from_model, baseline) -> VerifyOpts:
+        """verifyMatches' argument checks (and the baseline's), before the library is called"""
+        _check_max_px(max_px)
+        H = int(hypotheses)
+        if H < 1:
+            raise Fm3dError(ERR_INVALID, "hypotheses must be >= 1")
+        R = int(refine)
+        if not 0 <= R <= 16:
+            raise Fm3dError(ERR_INVALID, "refine must be in 0 .. 16")
+        b = float(baseline)
+        if pose_from_model and not (b > 0.0 and b != float("inf")):
+            raise Fm3dError(ERR_INVALID, "baseline must be finite and > 0")
+        return VerifyOpts(H, R, float(max_px), int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if pose_from_model else 0, 0, b)
+
+    def run_verified(self, max_px, hypotheses: int = 1024, seed: int = 0, refine: int = 0, pose_from_model: bool = False,
+                     baseline: float = 1.0, records_dev_ptr: int | None = None):
+        """fm3d_pipeline_run_verified (DESIGN.md §3.1d "In the pipeline"): run() with the staged pair's
+        matches verified on the device (verifyMatches' max_px, hypotheses, seed, refine) and only the
+        verified ones triangulated and optimised.  pose_from_model: the camera-2 pose comes from the
+        model (pose_from_epipolar over the verified matches, |t| = baseline) and STAYS installed in the
+        context; otherwise the context's pose is kept.  Returns (n_kept, stats dict, report dict):
+        matches, verified, best, roundsAdopted, poseInstalled, votes (4,), E (3, 3), g12 (4, 4),
+        verify_ms.  No model: zero records, the pose unchanged."""
+        o = self._verify_opts(max_px, hypotheses, seed, refine, pose_from_model, baseline)
+        n = ctypes.c_int(0)
+        st, rep = PipelineStats(), VerifyReport()
+        self.ctx.check(lib().fm3d_pipeline_run_verified(self.ctx.handle, ctypes.byref(o),
+                                                        ctypes.c_void_p(records_dev_ptr or 0), ctypes.byref(n),
+                                                        ctypes.byref(st), ctypes.byref(rep)))
+        return n.value, st.as_dict(), rep.as_dict()
+
+    def run_dlt_verified(self, max_px, hypotheses: int = 1024, seed: int = 0, refine: int = 0,
+                         pose_from_model: bool = False, baseline: float = 1.0):
+        """fm3d_pipeline_run_dlt_verified: run_dlt() on the verified matches, options as run_verified;
+        returns (n_inliers, stats dict, report dict).  dlt_results(stats["matches"], n_inliers) then
+        gives the verified matches and their points."""
+        o = self._verify_opts(max_px, hypotheses, seed, refine, pose_from_model, baseline)
+        n = ctypes.c_int(0)
+        st, rep = PipelineStats(), VerifyReport()
+        self.ctx.check(lib().fm3d_pipeline_run_dlt_verified(self.ctx.handle, ctypes.byref(o), ctypes.byref(n),
+                                                            ctypes.byref(st), ctypes.byref(rep)))
+        return n.value, st.as_dict(), rep.as_dict()
 
     def submit_dlt(self) -> None:
         """fm3d_pipeline_submit_dlt: C2's path queued on the context stream (returns at once)"""

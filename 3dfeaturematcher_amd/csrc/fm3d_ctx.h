@@ -149,6 +149,9 @@ struct fm3d_ctx {
     DevBuf records, recTmp, recFlag;
     DevBuf lmProj;  // camera-2 projection constants for the LM kernel (fm3d::ProjConst)
     DevBuf pcnt;    // the pipeline's device counts: [0] matches K, [1] inliers P, [2] kept
+    // fm3d_pipeline_run(_dlt)_verified: the verification's working memory (grown on demand, reused across
+    // pairs) and the compaction's output, swapped with `matches` once it holds the verified ones
+    DevBuf verWork, verMatches;
     // pinned staging: descriptors A / B (padded rows), keypoints, images, small tables, results
     HostBuf hA, hB, hK1, hK2, hImg, hTab, hProj, hSmall, hFlag;
     hipEvent_t evStage = nullptr;  // after the last H2D copy from the staging buffers
@@ -174,7 +177,9 @@ struct fm3d_ctx {
     int* frontHostCnt = nullptr;  // pipeline_front: the DLT kernel also stores (K, P) here (device pointer)
     int nccP = 0;          // points of the last successful fm3d_pipeline_run_ncc (its score rows)
     bool staged = false;
-    hipEvent_t ev[10] = {};  // [0..1] standalone LM, [2..7] pipeline stages, [8] submit start, [1] end
+    // [0..1] standalone LM, [2..7] pipeline stages ([4] and [9]: around the verification of
+    // fm3d_pipeline_run_verified), [8] submit start, [1] end
+    hipEvent_t ev[10] = {};
     std::string err;
 
     fm3d_ctx() = default;
@@ -202,6 +207,15 @@ inline int fail(fm3d_ctx* c, int code, const std::string& msg) {
 
 // the scan scratch and the count word of a compaction over n flags (fm3d_host.cpp)
 int ensure_scan_tmp(fm3d_ctx* c, int n);
+
+// fm3d_pipeline_run(_dlt)_verified's middle (fm3d_verify.cpp): the verification of the K matches in
+// c->matches against the staged keypoints, queued on the context stream in c->verWork; the verified
+// matches, compacted, take the place of c->matches and their count that of c->pcnt[0]; with
+// o->poseFromModel the pose candidates and their votes.  One host wait.  Fills rep's best, verified,
+// roundsAdopted, E, votes and verify_ms; *havePose: g12 holds fm3d_pose_from_epipolar's pose (not yet
+// installed).  K >= 8.
+int verify_staged(fm3d_ctx* c, const fm3d_verify_opts* o, int K, fm3d_verify_report* rep, bool* havePose,
+                  double g12[16]);
 
 }  // namespace fm3d_host
 

@@ -1174,11 +1174,11 @@ int stage_pipeline(fm3d_ctx* c, const void* descA, int nA, const void* descB, in
     return FM3D_OK;
 }
 
-// match -> NNDR -> compaction -> DLT triangulation -> compaction on the staged inputs (ev[2..5]),
-// sized by the query count: the match count K and the inlier count P stay on the device
-// (c->pcnt[0], [1]) and bound nothing the host launches, so the stages queue without a host
-// round trip (c->matches, c->pts, c->srcIdx hold K / P entries)
-int pipeline_front(fm3d_ctx* c) {
+// The front half on the staged inputs (ev[2..5]) is match -> NNDR -> compaction (front_match), then DLT
+// triangulation -> compaction (front_dlt), sized by the query count: the match count K and the
+// inlier count P stay on the device (c->pcnt[0], [1]) and bound nothing the host launches, so the
+// stages queue without a host round trip (c->matches, c->pts, c->srcIdx hold K / P entries)
+int front_match(fm3d_ctx* c) {
     const int nA = c->stNA, nB = c->stNB;
     int r;
     hipEvent_t* ev = c->ev;
@@ -1210,6 +1210,14 @@ int pipeline_front(fm3d_ctx* c) {
     // FM3D_STAGE_EVENTS=0 leaves only the step's own ev[2] / ev[1]
     c->stageEv = stage_events();
     if (c->stageEv) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+    return FM3D_OK;
+}
+
+int front_dlt(fm3d_ctx* c) {
+    const int nA = c->stNA;
+    int r;
+    hipEvent_t* ev = c->ev;
+    int* cnt = c->pcnt.as<int>();
     // a4, a5: triangulate (matches are device resident; K <= nA)
     HIPCHK(c, c->triPts.ensure((size_t)(nA + 1) * 3 * sizeof(double)));
     HIPCHK(c, c->triMask.ensure((size_t)(nA + 1) * sizeof(int)));
@@ -1239,6 +1247,12 @@ int pipeline_front(fm3d_ctx* c) {
     HIPCHK(c, hipGetLastError());
     if (c->stageEv) HIPCHK(c, hipEventRecord(ev[5], c->stream));
     return FM3D_OK;
+}
+
+int pipeline_front(fm3d_ctx* c) {
+    int r;
+    if ((r = front_match(c))) return r;
+    return front_dlt(c);
 }
 
 // the survivor records of c's pair (after its LM normals, in stream order), then one D2H of the
@@ -1555,6 +1569,26 @@ int queue_front_counts(fm3d_ctx* c) {
     return FM3D_OK;
 }
 
+// after ev[1] of queue_front_counts: the counts it left in page-locked memory, and the stage times
+void report_front_counts(fm3d_ctx* c, int* nInliers, fm3d_pipeline_stats* stats) {
+    const PipeSmall* hs = c->hSmall.as<PipeSmall>();
+    const int K = hs->cnt[0], P = hs->cnt[1];
+    c->stK = K;
+    c->stP = P;
+    if (nInliers) *nInliers = P;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->queries = c->stNA;
+        stats->trains = c->stNB;
+        stats->matches = K;
+        stats->inliers = P;
+        float ms;
+        stage_times(c, stats);
+        hipEventElapsedTime(&ms, c->ev[2], c->ev[1]);
+        stats->total_ms = ms;
+    }
+}
+
 // after a speculative front half (stage_descriptors' speculate): when the pack kernel flagged an
 // element that is not an integer in [0, 255], the float rows (still on the device) go through the
 // float matchers and the front half runs again, as the non-speculative staging would have run it
@@ -1612,22 +1646,7 @@ int fm3d_pipeline_wait_dlt(fm3d_ctx* c, int* nInliers, fm3d_pipeline_stats* stat
     HIPCHK(c, hipEventSynchronize(ev[1]));
     int r;
     if ((r = redo_float_front(c))) return r;
-    const PipeSmall* hs = c->hSmall.as<PipeSmall>();
-    const int K = hs->cnt[0], P = hs->cnt[1];
-    c->stK = K;
-    c->stP = P;
-    if (nInliers) *nInliers = P;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->queries = c->stNA;
-        stats->trains = c->stNB;
-        stats->matches = K;
-        stats->inliers = P;
-        float ms;
-        stage_times(c, stats);
-        hipEventElapsedTime(&ms, ev[2], ev[1]);
-        stats->total_ms = ms;
-    }
+    report_front_counts(c, nInliers, stats);
     return FM3D_OK;
 }
 
@@ -1635,6 +1654,121 @@ int fm3d_pipeline_run_dlt(fm3d_ctx* c, int* nInliers, fm3d_pipeline_stats* stats
     int r;
     if ((r = fm3d_pipeline_submit_dlt(c))) return r;
     return fm3d_pipeline_wait_dlt(c, nInliers, stats);
+}
+
+}  // extern "C"
+namespace {
+// fm3d_pipeline_run(_dlt)_verified's argument rules, before any launch
+int check_verified(fm3d_ctx* c, const fm3d_verify_opts* o, const fm3d_verify_report* rep) {
+    if (!c || !o || !rep) return fail(c, FM3D_ERR_INVALID, "null argument");
+    if (!c->staged) return fail(c, FM3D_ERR_INVALID, "fm3d_pipeline_upload not called");
+    PENDING_CHECK(c);
+    if (o->hypotheses < 1) return fail(c, FM3D_ERR_INVALID, "hypotheses must be >= 1");
+    if (o->refineIters < 0 || o->refineIters > 16) return fail(c, FM3D_ERR_INVALID, "refineIters must be in 0 .. 16");
+    if (!good_max_px(o->maxPx)) return fail(c, FM3D_ERR_INVALID, "maxPx must be finite and > 0");
+    if (o->reserved != 0) return fail(c, FM3D_ERR_INVALID, "reserved must be 0");
+    if (o->poseFromModel != 0 && o->poseFromModel != 1) return fail(c, FM3D_ERR_INVALID, "poseFromModel must be 0 or 1");
+    if (o->poseFromModel) {
+        if (!good_max_px(o->baseline)) return fail(c, FM3D_ERR_INVALID, "baseline must be finite and > 0");
+        if (c->s.guidedMatchPx > 0.)
+            return fail(c, FM3D_ERR_INVALID,
+                        "poseFromModel with guidedMatchPx > 0: the gate needs the pose this call is about to find");
+    }
+    if (c->stQueryOffset != 0)
+        return fail(c, FM3D_ERR_UNSUPPORTED, "a staged queryOffset != 0: a share sees only its own matches");
+    if (o->hypotheses > fm3d::kVerifyMaxHyps) return fail(c, FM3D_ERR_UNSUPPORTED, "more than 2^20 hypotheses");
+    return FM3D_OK;
+}
+
+// The match half, one wait for K, the verification of those matches where they lie (verify_staged:
+// its own wait), and the pose's installation.  *go: a model (and, when asked for, its pose) exists, the
+// verified matches and their count are where front_dlt reads them.  Otherwise nothing further may be
+// launched on this pair: its counts are zero on both sides.
+int front_verified(fm3d_ctx* c, const fm3d_verify_opts* o, fm3d_verify_report* rep, bool* go) {
+    int r;
+    *go = false;
+    std::memset(rep, 0, sizeof(*rep));
+    rep->best = -1;
+    if ((r = front_match(c))) return r;
+    int* cnt = c->pcnt.as<int>();
+    int K = 0;
+    HIPCHK(c, hipMemcpyAsync(&K, cnt + 0, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (K < 0 || K > c->stNA) return fail(c, FM3D_ERR_HIP, "match count out of range");
+    rep->matches = K;
+    if (K >= 8) {  // fewer: no sample exists, every hypothesis is invalid
+        bool havePose = false;
+        double g[16];
+        if ((r = verify_staged(c, o, K, rep, &havePose, g))) return r;
+        *go = rep->best >= 0 && (!o->poseFromModel || havePose);
+        if (*go && o->poseFromModel) {
+            install_g12(c, g);
+            rep->poseInstalled = 1;
+        }
+    }
+    std::memcpy(rep->g12, c->g12, sizeof(rep->g12));
+    if (!*go) {
+        rep->verified = 0;
+        for (int k = 0; k < 4; k++) rep->votes[k] = 0;
+        c->stK = c->stP = 0;
+        HIPCHK(c, hipMemsetAsync(cnt, 0, 4 * sizeof(int), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return FM3D_OK;
+}
+
+void empty_stats(const fm3d_ctx* c, fm3d_pipeline_stats* stats) {
+    if (!stats) return;
+    std::memset(stats, 0, sizeof(*stats));
+    stats->queries = c->stNA;
+    stats->trains = c->stNB;
+}
+}  // namespace
+extern "C" {
+
+int fm3d_pipeline_run_verified(fm3d_ctx* c, const fm3d_verify_opts* o, fm3d_record* recordsDev, int* nKept,
+                               fm3d_pipeline_stats* stats, fm3d_verify_report* rep) {
+    int r;
+    if ((r = check_verified(c, o, rep))) return r;
+    hipSetDevice(c->device);
+    bool go;
+    if ((r = front_verified(c, o, rep, &go))) return r;
+    if (!go) {
+        if (nKept) *nKept = 0;
+        empty_stats(c, stats);
+        return FM3D_OK;
+    }
+    fm3d_lm_stats ls{};
+    if ((r = front_dlt(c))) return r;
+    if ((r = run_lm(c, c->stNA, c->pcnt.as<int>() + 1, &ls, c->ev[6], c->ev[7]))) return r;
+    if ((r = enqueue_epilogue(c, recordsDev, c->lmStat.p))) return r;
+    return finalize_full(c, ls, c->ev[2], false, nKept, stats);
+}
+
+int fm3d_pipeline_run_dlt_verified(fm3d_ctx* c, const fm3d_verify_opts* o, int* nInliers, fm3d_pipeline_stats* stats,
+                                   fm3d_verify_report* rep) {
+    int r;
+    if ((r = check_verified(c, o, rep))) return r;
+    hipSetDevice(c->device);
+    bool go;
+    if ((r = front_verified(c, o, rep, &go))) return r;
+    if (!go) {
+        if (nInliers) *nInliers = 0;
+        empty_stats(c, stats);
+        return FM3D_OK;
+    }
+    // as queue_front_counts: the DLT kernel stores (K, P) in page-locked memory itself
+    HIPCHK(c, c->hSmall.ensure(sizeof(PipeSmall)));
+    void* dcnt = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer(&dcnt, c->hSmall.as<PipeSmall>()->cnt, 0));
+    c->frontHostCnt = (int*)dcnt;
+    r = front_dlt(c);
+    c->frontHostCnt = nullptr;
+    if (r) return r;
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev[1]));
+    report_front_counts(c, nInliers, stats);
+    return FM3D_OK;
 }
 
 int fm3d_pipeline_submit_ncc(fm3d_ctx* c, int Hphi, int Htheta, double span) {

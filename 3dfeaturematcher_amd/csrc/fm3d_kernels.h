@@ -343,6 +343,14 @@ size_t verify_refine_bytes(int M, int rounds);
 void launch_verify_refine(int M, int rounds, double tau2, const double* xy, const int* count, const int* best,
                           double* E, void* work, int* flag, uint8_t* mask, int** roundCounts, double** roundModels,
                           int** adopted, hipStream_t s);
+// The pose stage behind the final model (launch_verify with its mask, or launch_verify_refine): the two
+// rotations and u_2 of E (fm3d_epi8::pose_candidates; cand: 21 doubles, R[0], R[1], u_2), *valid = 0
+// when best < 0 or E has no decomposition, and votes[4]: per candidate the matches with flag != 0 that
+// fm3d_epi8::pose_vote puts in front of both cameras.  work: verify_pose_bytes(), 8-byte aligned, one
+// block (cand, then the integers) that a single copy brings to the host; the outputs point into it.
+size_t verify_pose_bytes();
+void launch_verify_pose(int M, const double* xy, const int* flag, const int* best, const double* E, void* work,
+                        double** cand, int** valid, int** votes, hipStream_t s);
 
 // ---------------- triangulation ----------------
 struct TriParams {

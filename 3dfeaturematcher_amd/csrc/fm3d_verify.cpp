@@ -1,6 +1,7 @@
 // fm3d_verify.cpp -- geometric verification, the host side: fm3d_verify_matches'
-// orchestration (with the refinement rounds of fm3d_verify_matches_refined) and the context-free
-// algebra (sampler, eight-point model, count, normal matrix and refit, pose from E).
+// orchestration (with the refinement rounds of fm3d_verify_matches_refined), the same stage on a staged
+// pipeline pair (verify_staged, for fm3d_pipeline_run(_dlt)_verified in fm3d_host.cpp) and the
+// context-free algebra (sampler, eight-point model, count, normal matrix and refit, pose from E).
 // The arithmetic is include/fm3d_epi8.h's; the kernels are fm3d_verify.hip's.
 #include <hip/hip_runtime.h>
 
@@ -19,7 +20,7 @@ using namespace fm3d_host;
 
 namespace {
 
-// one allocation per call, carved in 256-byte steps (the stage keeps nothing in the context)
+// one block carved in 256-byte steps: a local one per fm3d_verify_matches call, the context's for a staged pair
 struct Carver {
     size_t off = 0;
     size_t take(size_t bytes) {
@@ -28,14 +29,6 @@ struct Carver {
         return at;
     }
 };
-
-double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-void cross3(const double a[3], const double b[3], double c[3]) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
 
 }  // namespace
 
@@ -79,47 +72,16 @@ int fm3d_epipolar_count(const double E[9], const double* x1, const double* x2, i
 int fm3d_pose_from_epipolar(const double E[9], const double* x1, const double* x2, int n, double baseline,
                             double g12[16], int32_t votes[4]) {
     if (!E || !g12 || n < 0 || ((!x1 || !x2) && n)) return FM3D_ERR_INVALID;
-    double u[3][3], v[3][3], W[3];
-    {
-        double u2[2][3], v2[2][3];
-        if (!fm3d_epi8::svd_e(E, u2, v2, W)) return 1;
-        std::memcpy(u, u2, sizeof(u2));
-        std::memcpy(v, v2, sizeof(v2));
-    }
-    cross3(u[0], u[1], u[2]);
-    cross3(v[0], v[1], v[2]);
-    // U W V^T = u1 v0^T - u0 v1^T + u2 v2^T and U W^T V^T = -u1 v0^T + u0 v1^T + u2 v2^T
-    double R[2][9];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            R[0][r * 3 + c] = (u[1][r] * v[0][c] + (-u[0][r]) * v[1][c]) + u[2][r] * v[2][c];
-            R[1][r * 3 + c] = ((-u[1][r]) * v[0][c] + u[0][r] * v[1][c]) + u[2][r] * v[2][c];
-        }
+    double R[2][9], u2[3];
+    if (!fm3d_epi8::pose_candidates(E, R, u2)) return 1;
     int vt[4] = {0, 0, 0, 0};
     for (int k = 0; k < 4; k++) {
-        const double* Rk = R[k >> 1];
-        const double sg = (k & 1) ? -1. : 1.;
-        const double t[3] = {sg * u[2][0], sg * u[2][1], sg * u[2][2]};
-        for (int i = 0; i < n; i++) {
-            const double p[3] = {x1[2 * i], x1[2 * i + 1], 1.}, b[3] = {x2[2 * i], x2[2 * i + 1], 1.};
-            const double a[3] = {dot3(Rk, p), dot3(Rk + 3, p), dot3(Rk + 6, p)};
-            const double aa = dot3(a, a), ab = dot3(a, b), bb = dot3(b, b), at = dot3(a, t), bt = dot3(b, t);
-            const double det = aa * bb - ab * ab;
-            const double z1 = (ab * bt - bb * at) / det, z2 = (aa * bt - ab * at) / det;
-            vt[k] += (z1 > 0. && z2 > 0.) ? 1 : 0;
-        }
+        double t[3];
+        fm3d_epi8::pose_direction(k, u2, t);
+        for (int i = 0; i < n; i++)
+            vt[k] += fm3d_epi8::pose_vote(R[k >> 1], t, x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1]) ? 1 : 0;
     }
-    int bk = 0;
-    for (int k = 1; k < 4; k++)
-        if (vt[k] > vt[bk]) bk = k;
-    const double* Rb = R[bk >> 1];
-    const double sg = (bk & 1) ? -1. : 1.;
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) g12[r * 4 + c] = Rb[r * 3 + c];
-        g12[r * 4 + 3] = baseline * (sg * u[2][r]);
-    }
-    g12[12] = g12[13] = g12[14] = 0.;
-    g12[15] = 1.;
+    fm3d_epi8::pose_g12(fm3d_epi8::pose_pick(vt), R, u2, baseline, g12);
     if (votes)
         for (int k = 0; k < 4; k++) votes[k] = vt[k];
     return 0;
@@ -178,6 +140,80 @@ int fm3d_epipolar_refit(const double E[9], const double* x1, const double* x2, i
     normal45(E, x1, x2, n, tau * tau, N45);
     fm3d_epi8::Mat99 S, V;
     return fm3d_epi8::refit45(N45, S, V, Eout) ? 0 : 1;
+}
+
+int fm3d_host::verify_staged(fm3d_ctx* c, const fm3d_verify_opts* o, int K, fm3d_verify_report* rep, bool* havePose,
+                             double g12[16]) {
+    const int M = K, H = o->hypotheses, R = o->refineIters;
+    const bool pose = o->poseFromModel != 0;
+    const fm3d::Camera& cam = c->cam;
+    const double tau = o->maxPx * 2.0 / (cam.fx + cam.fy);
+    const double tau2 = tau * tau;
+    hipStream_t st = c->stream;
+    *havePose = false;
+    // fm3d_verify_matches_refined's carving, without the inputs: they are the context's
+    const int Mpad = fm3d::verify_pad(M);
+    Carver cv;
+    const size_t oXY = cv.take((size_t)4 * Mpad * sizeof(double));
+    const size_t oMod = cv.take((size_t)H * 9 * sizeof(double)), oCnt = cv.take((size_t)H * sizeof(int));
+    const size_t oBest = cv.take(sizeof(int)), oE = cv.take(9 * sizeof(double));
+    const size_t oFlag = cv.take((size_t)M * sizeof(int)), oMask = cv.take((size_t)M);
+    const size_t oRef = R ? cv.take(fm3d::verify_refine_bytes(M, R)) : 0;
+    const size_t oPose = cv.take(fm3d::verify_pose_bytes());
+    HIPCHK(c, c->verWork.ensure(cv.off));
+    HIPCHK(c, c->verMatches.ensure((size_t)(c->stNA + 1) * sizeof(fm3d_dmatch)));
+    char* const pool = c->verWork.as<char>();
+    int* const cnt = c->pcnt.as<int>();
+    HIPCHK(c, hipEventRecord(c->ev[4], st));
+    fm3d::launch_verify(cam, c->kp1.as<fm3d_point2f>(), c->kp2.as<fm3d_point2f>(), c->matches.as<fm3d_dmatch>(), M, H,
+                        o->seed, tau2, c->nCU, (double*)(pool + oXY), (double*)(pool + oMod), (int*)(pool + oCnt),
+                        (int*)(pool + oBest), (double*)(pool + oE), (int*)(pool + oFlag), (uint8_t*)(pool + oMask), st,
+                        R == 0);
+    int *dRoundCounts = nullptr, *dAdopted = nullptr;
+    double* dRoundModels = nullptr;
+    if (R)
+        fm3d::launch_verify_refine(M, R, tau2, (const double*)(pool + oXY), (const int*)(pool + oCnt),
+                                   (const int*)(pool + oBest), (double*)(pool + oE), pool + oRef, (int*)(pool + oFlag),
+                                   (uint8_t*)(pool + oMask), &dRoundCounts, &dRoundModels, &dAdopted, st);
+    // the verified matches and their count where the DLT reads them (c->scanTmp holds stNA >= M items)
+    fm3d::launch_compact_dmatch(c->matches.as<fm3d_dmatch>(), (const int*)(pool + oFlag), M,
+                                c->verMatches.as<fm3d_dmatch>(), cnt + 0, c->scanTmp.p, st);
+    double* dCand = nullptr;
+    int *dValid = nullptr, *dVotes = nullptr;
+    if (pose)
+        fm3d::launch_verify_pose(M, (const double*)(pool + oXY), (const int*)(pool + oFlag), (const int*)(pool + oBest),
+                                 (const double*)(pool + oE), pool + oPose, &dCand, &dValid, &dVotes, st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev[9], st));
+    std::swap(c->matches, c->verMatches);
+    struct {
+        double cand[fm3d_epi8::kPoseDoubles];
+        int32_t pv[8];
+    } hp{};
+    static_assert(sizeof(hp) == fm3d_epi8::kPoseDoubles * sizeof(double) + 8 * sizeof(int), "the pose block's layout");
+    int n = 0, best = -1, adopted = 0;
+    HIPCHK(c, hipMemcpyAsync(&n, cnt + 0, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&best, pool + oBest, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(rep->E, pool + oE, 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (R) HIPCHK(c, hipMemcpyAsync(&adopted, dAdopted, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (pose) HIPCHK(c, hipMemcpyAsync(&hp, pool + oPose, sizeof(hp), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (n < 0 || n > M) return fail(c, FM3D_ERR_HIP, "verify: inlier count out of range");
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev[4], c->ev[9]);
+    rep->verify_ms = ms;
+    rep->best = best;
+    rep->verified = best >= 0 ? n : 0;
+    rep->roundsAdopted = adopted;
+    if (pose && best >= 0 && hp.pv[0]) {
+        double Rc[2][9], u2[3];
+        std::memcpy(Rc, hp.cand, sizeof(Rc));
+        std::memcpy(u2, hp.cand + 18, sizeof(u2));
+        for (int k = 0; k < 4; k++) rep->votes[k] = hp.pv[1 + k];
+        fm3d_epi8::pose_g12(fm3d_epi8::pose_pick(hp.pv + 1), Rc, u2, o->baseline, g12);
+        *havePose = true;
+    }
+    return FM3D_OK;
 }
 
 int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm3d_point2f* kpts2, int n2,

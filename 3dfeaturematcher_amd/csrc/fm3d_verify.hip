@@ -1,6 +1,7 @@
 // fm3d_verify.hip -- geometric verification of matches: a RANSAC fit of the
-// essential matrix, every hypothesis scored against every match, and the rounds of a least-squares
-// refit of the best model on its inliers.  The arithmetic is include/fm3d_epi8.h's (shared with the
+// essential matrix, every hypothesis scored against every match, the rounds of a least-squares
+// refit of the best model on its inliers, and the final model's pose candidates with their cheirality
+// votes.  The arithmetic is include/fm3d_epi8.h's (shared with the
 // host entry points and restated in tests/verify_pyref.py and tests/verify_refit_pyref.py); the
 // kernels only distribute it.
 #include <hip/hip_runtime.h>
@@ -327,7 +328,97 @@ __global__ __launch_bounds__(64) void verify_adopt_kernel(int r, int* __restrict
     }
 }
 
+// ---------------- the pose of the final model (fm3d_pipeline_run_verified) ----------------
+// pv: the pose stage's integers -- the valid flag, then the four candidates' votes
+enum { kPvValid = 0, kPvVotes = 1 };
+
+// One wave behind the final model: thread 0 builds the two rotations and u_2 of E (cand:
+// fm3d_epi8::kPoseDoubles doubles, zero when there is none) and the valid flag; the votes start at 0.
+__global__ __launch_bounds__(64) void verify_pose_candidates_kernel(const int* __restrict__ best,
+                                                                    const double* __restrict__ Eb,
+                                                                    double* __restrict__ cand, int* __restrict__ pv) {
+    if (threadIdx.x != 0) return;
+    double E[9], R[2][9], u2[3];
+#pragma unroll
+    for (int k = 0; k < 9; k++) E[k] = Eb[k];
+    const bool ok = *best >= 0 && fm3d_epi8::pose_candidates(E, R, u2);
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        cand[k] = ok ? R[0][k] : 0.;
+        cand[9 + k] = ok ? R[1][k] : 0.;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) cand[18 + k] = ok ? u2[k] : 0.;
+    pv[kPvValid] = ok ? 1 : 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) pv[kPvVotes + k] = 0;
+}
+
+// Workgroup bx: the votes of tile bx, in verify_score_kernel's shape.  A lane keeps four slots'
+// coordinates; a slot votes only when it is a match (i < M: the pad holds NaN and has no flag) that the
+// final model accepts (flag).  The 21 candidate doubles have one address per wave (scalar loads); a
+// wave counts with ballots, the four waves add in LDS, and one atomicAdd per (workgroup, candidate)
+// with a non-zero count goes to the votes -- integers, exact in any order.
+__global__ __launch_bounds__(kScoreThreads) void verify_pose_vote_kernel(const double* __restrict__ xy, int M, int Mpad,
+                                                                         const int* __restrict__ flag,
+                                                                         const double* __restrict__ cand,
+                                                                         int* __restrict__ pv) {
+    __shared__ int sCnt[kScoreThreads / 64][4];
+    if (!pv[kPvValid]) return;  // the same word for every thread: all leave, or none
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double x1[kScorePer], y1[kScorePer], x2[kScorePer], y2[kScorePer];
+    bool in[kScorePer];
+#pragma unroll
+    for (int k = 0; k < kScorePer; k++) {
+        const size_t i = (size_t)blockIdx.x * kVerifyTile + k * kScoreThreads + tid;  // < Mpad
+        x1[k] = xy[i];
+        y1[k] = xy[(size_t)Mpad + i];
+        x2[k] = xy[(size_t)2 * Mpad + i];
+        y2[k] = xy[(size_t)3 * Mpad + i];
+        in[k] = i < (size_t)M && flag[i] != 0;
+    }
+    double R[2][9], u2[3];
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        R[0][k] = cand[k];
+        R[1][k] = cand[9 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) u2[k] = cand[18 + k];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        double t[3];
+        fm3d_epi8::pose_direction(j, u2, t);
+        int c = 0;
+#pragma unroll
+        for (int k = 0; k < kScorePer; k++)
+            c += __popcll(__ballot(in[k] && fm3d_epi8::pose_vote(R[j >> 1], t, x1[k], y1[k], x2[k], y2[k])));
+        if (lane == 0) sCnt[wave][j] = c;
+    }
+    __syncthreads();
+    if (tid < 4) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < kScoreThreads / 64; w++) s += sCnt[w][tid];
+        if (s) atomicAdd(&pv[kPvVotes + tid], s);
+    }
+}
+
 }  // namespace
+
+size_t verify_pose_bytes() { return fm3d_epi8::kPoseDoubles * sizeof(double) + 8 * sizeof(int); }
+
+void launch_verify_pose(int M, const double* xy, const int* flag, const int* best, const double* E, void* work,
+                        double** cand, int** valid, int** votes, hipStream_t s) {
+    const int Mpad = verify_pad(M);
+    double* cd = (double*)work;
+    int* pv = (int*)(cd + fm3d_epi8::kPoseDoubles);
+    verify_pose_candidates_kernel<<<1, 64, 0, s>>>(best, E, cd, pv);
+    verify_pose_vote_kernel<<<Mpad / kVerifyTile, kScoreThreads, 0, s>>>(xy, M, Mpad, flag, cd, pv);
+    *cand = cd;
+    *valid = pv + kPvValid;
+    *votes = pv + kPvVotes;
+}
 
 size_t verify_refine_bytes(int M, int rounds) {
     const size_t tiles = (size_t)verify_pad(M) / kVerifyTile;

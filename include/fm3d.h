@@ -634,6 +634,64 @@ int fm3d_pipeline_submit_dlt_pair(fm3d_ctx *ctx, const void *descA, int nA, cons
 /* after fm3d_pipeline_run(_dlt): the compacted matches (K), the inlier points (P x 3 doubles, the
    z-filtered triangulation in match order) and each point's match index (P); any may be NULL */
 int fm3d_pipeline_dlt_download(fm3d_ctx *ctx, fm3d_dmatch *matches, double *points, int32_t *matchIdx);
+
+/* ---------------- the staged pipeline on verified matches ("In the pipeline") ---------------- */
+typedef struct fm3d_verify_opts {
+    int32_t hypotheses;     /* 1 .. 2^20 */
+    int32_t refineIters;    /* 0 .. 16 */
+    double maxPx;           /* finite, > 0 (fm3d_verify_matches' unit) */
+    uint64_t seed;
+    int32_t poseFromModel;  /* 0: keep the context's g12, only filter the matches
+                               1: install the model's pose before the DLT */
+    int32_t reserved;       /* 0 */
+    double baseline;        /* poseFromModel = 1: |t| of the installed g12, finite, > 0 */
+} fm3d_verify_opts;
+
+typedef struct fm3d_verify_report {
+    int32_t matches;        /* K: what the match stage kept (NNDR, gate, cross-check) */
+    int32_t verified;       /* the matches the final model accepts = what the DLT consumed */
+    int32_t best;           /* the RANSAC's best hypothesis, -1: none */
+    int32_t roundsAdopted;
+    int32_t poseInstalled;  /* 1 iff g12 below was installed in the context */
+    int32_t votes[4];       /* poseFromModel = 1: fm3d_pose_from_epipolar's votes over the verified matches */
+    double E[9];            /* the final model (zero when best == -1) */
+    double g12[16];         /* the pose the DLT and the LM ran with */
+    double verify_ms;       /* HIP events around the verification stage */
+} fm3d_verify_report;
+
+/* fm3d_pipeline_run and fm3d_pipeline_run_dlt with the geometric verification between the match stage
+   and the DLT, on the inputs of fm3d_pipeline_upload and where they lie (no keypoint or match leaves the
+   device).  Synchronous.
+   - The match stage is the pipeline's own, with Fm3d.guidedMatchPx and Fm3d.crossCheck as set:
+     report.matches and the matches are what fm3d_pipeline_run_dlt would report.
+   - The verification is fm3d_verify_matches_refined on exactly those matches and the staged keypoints,
+     with the options' hypotheses, maxPx, seed and refineIters: report.best, E, roundsAdopted and the
+     inlier mask are that call's, bit for bit.
+   - The verified matches, stably compacted, replace the pair's matches: stats.matches ==
+     report.verified, and fm3d_pipeline_dlt_download afterwards returns the verified matches and their
+     points.  stats.triangulate_ms spans the verification too (it lies between the match stage's end
+     and the DLT's); report.verify_ms is the verification's own time.
+   - poseFromModel = 1: g12 = fm3d_pose_from_epipolar(E, x1, x2, n, baseline) over the verified
+     matches' coordinates (the verification's own doubles), the votes counted on the device; report.g12
+     and votes are that host function's, bit for bit.  The pose is installed exactly as
+     fm3d_set_g12(ctx, g12) would install it BEFORE the DLT, and it STAYS installed after the call:
+     later calls on the context (fm3d_pipeline_run, fm3d_triangulate, fm3d_get_camera2, ...) see it.
+   - poseFromModel = 0: the context's pose is untouched and report.g12 is the context's.
+   - No model (best == -1: fewer than 8 matches, or no valid hypothesis) or a failed pose
+     (fm3d_pose_from_epipolar would return 1): verified = 0, zero records / inliers, FM3D_OK,
+     poseInstalled = 0, the context's pose unchanged, report.g12 the context's; neither the DLT nor
+     the LM is launched.
+   FM3D_ERR_INVALID, before any launch: a null context, opts or report; nothing staged, or a pending
+   submit; hypotheses < 1, refineIters outside 0 .. 16, a bad maxPx, poseFromModel outside {0, 1},
+   reserved != 0; poseFromModel = 1 with a baseline that is not finite and > 0, or with
+   Fm3d.guidedMatchPx > 0 (the gate needs the pose this call is about to find).
+   FM3D_ERR_UNSUPPORTED: a staged queryOffset != 0 (a share sees only its own matches); more than 2^20
+   hypotheses.  The multi-GPU calls have no counterpart.
+   The host waits twice before the DLT (for K, then for the model, the pose candidates and the votes). */
+int fm3d_pipeline_run_verified(fm3d_ctx *ctx, const fm3d_verify_opts *opts, fm3d_record *recordsDev, int *nKept,
+                               fm3d_pipeline_stats *stats, fm3d_verify_report *report);
+int fm3d_pipeline_run_dlt_verified(fm3d_ctx *ctx, const fm3d_verify_opts *opts, int *nInliers,
+                                   fm3d_pipeline_stats *stats, fm3d_verify_report *report);
 /* BASELINE.json's C3 as worded ("Hamming popcount match + 64x64 patch NCC over 16 normal hypotheses"):
    match -> NNDR -> triangulate, then fm3d_ncc_hypotheses' scoring of every inlier on the device
    (pixelsRay 32 gives the 64 x 64 neighbourhood); *nPoints = inliers scored; stats.lm_ms is the NCC

@@ -8,7 +8,8 @@
  * kernels of fm3d_verify.hip and the numpy restatement (tests/verify_pyref.py) give the same bits.
  * The refit of a model on its own inliers follows: the 45 sums of the normal matrix in a fixed order,
  * a cyclic Jacobi eigen-iteration on the symmetric 9 x 9 and the same projection
- * (tests/verify_refit_pyref.py).  This header is the only place the arithmetic lives.
+ * (tests/verify_refit_pyref.py).  Last, the pose of a model: the four decompositions and one pair's
+ * cheirality vote (verify_pyref.pose).  This header is the only place the arithmetic lives.
  */
 #ifndef FM3D_EPI8_H
 #define FM3D_EPI8_H
@@ -347,6 +348,79 @@ FM3D_CVSVD_HD bool refit45(const double* N45, Mat& S, Mat& V, double E[9]) {
     const bool ok = refit_load(N45, S);
     if (ok) jacobi_null9(S, V, e, OneThread());
     return refit_project(ok, e, E);
+}
+
+// ---------------- the pose from a model ("Pose") ----------------
+
+constexpr int kPoseDoubles = 21;  // the candidates as one block: R[0] (9), R[1] (9), u_2 (3)
+
+FM3D_CVSVD_HD double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+FM3D_CVSVD_HD void cross3(const double a[3], const double b[3], double c[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// The four decompositions of E share two rotations and one direction: with svd_e's u_0, u_1, v_0, v_1,
+// u_2 = u_0 x u_1 and v_2 = v_0 x v_1,
+//   R[0] = U W V^T   =  u_1 v_0^T - u_0 v_1^T + u_2 v_2^T,
+//   R[1] = U W^T V^T = -u_1 v_0^T + u_0 v_1^T + u_2 v_2^T   (row-major),
+// and candidate k = 0 .. 3 is (R[k >> 1], t = u_2 for an even k, -u_2 for an odd one).  False when
+// svd_e fails (R and u2 are then not written).
+FM3D_CVSVD_HD bool pose_candidates(const double E[9], double (&R)[2][9], double (&u2)[3]) {
+    double u[2][3], v[2][3], W[3], v2[3];
+    if (!svd_e(E, u, v, W)) return false;
+    cross3(u[0], u[1], u2);
+    cross3(v[0], v[1], v2);
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            R[0][r * 3 + c] = (u[1][r] * v[0][c] + (-u[0][r]) * v[1][c]) + u2[r] * v2[c];
+            R[1][r * 3 + c] = ((-u[1][r]) * v[0][c] + u[0][r] * v[1][c]) + u2[r] * v2[c];
+        }
+    return true;
+}
+
+// candidate k's translation direction
+FM3D_CVSVD_HD void pose_direction(int k, const double u2[3], double t[3]) {
+    const double sg = (k & 1) ? -1. : 1.;
+#pragma unroll
+    for (int j = 0; j < 3; j++) t[j] = sg * u2[j];
+}
+
+// One pair's vote for (R, t): the depths z1, z2 of the point nearest both rays z1 a and z2 b - t, with
+// a = R (x1, y1, 1) and b = (x2, y2, 1), are both > 0.  The two quotients are formed: a sign test in
+// their place would vote differently when one underflows to zero.
+FM3D_CVSVD_HD bool pose_vote(const double R[9], const double t[3], double x1, double y1, double x2, double y2) {
+    const double p[3] = {x1, y1, 1.}, b[3] = {x2, y2, 1.};
+    const double a[3] = {dot3(R, p), dot3(R + 3, p), dot3(R + 6, p)};
+    const double aa = dot3(a, a), ab = dot3(a, b), bb = dot3(b, b), at = dot3(a, t), bt = dot3(b, t);
+    const double det = aa * bb - ab * ab;
+    const double z1 = (ab * bt - bb * at) / det, z2 = (aa * bt - ab * at) / det;
+    return z1 > 0. && z2 > 0.;
+}
+
+// the candidate with most votes, the lowest index on ties
+FM3D_CVSVD_HD int pose_pick(const int votes[4]) {
+    int bk = 0;
+    for (int k = 1; k < 4; k++)
+        if (votes[k] > votes[bk]) bk = k;
+    return bk;
+}
+
+// g12 = [R | baseline t] of candidate k, row-major 4 x 4
+FM3D_CVSVD_HD void pose_g12(int k, const double (&R)[2][9], const double u2[3], double baseline, double g12[16]) {
+    const double* Rb = R[k >> 1];
+    double t[3];
+    pose_direction(k, u2, t);
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) g12[r * 4 + c] = Rb[r * 3 + c];
+        g12[r * 4 + 3] = baseline * t[r];
+    }
+    g12[12] = g12[13] = g12[14] = 0.;
+    g12[15] = 1.;
 }
 
 }  // namespace fm3d_epi8
