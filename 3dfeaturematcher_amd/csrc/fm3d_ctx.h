@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -81,6 +82,48 @@ struct PipeSmall {
     unsigned long long lm[26];      // the LM launch's counters (fm3d_lm2.hip statPass layout)
 };
 
+// one direction's private buffers of a k = 2 search (knn2_search, fm3d_matching.cpp)
+struct KnnWork {
+    DevBuf cq, ct;            // u8: query constants, packed train constants
+    DevBuf q8, t8;            // 256-bit rows unpacked: queries 0/1, train rows -1/+1
+    DevBuf partIdx, partKey;  // per-part top-2 lists of the split matchers
+    DevBuf pairs;             // float rows: the row-pair copy of the train side
+    DevBuf idx, key, fkey;    // the merged top-2 lists
+};
+
+// The staged pair's state: what is queued on the context stream and not yet waited for.
+//
+//   state        entered by                                   left (to Idle) by
+//   Idle         create; every wait; a run_* that returned    --
+//   Full         submit (no leader), internal_enqueue;        wait, internal_finish
+//                from MemberFront: the leader's next submit,
+//                wait's or internal_flush's own LM
+//   MemberFront  submit on a link member (front half only)    (to Full, see there)
+//   DltFront     submit_dlt, submit_dlt_pair                  wait_dlt
+//   Ncc          submit_ncc                                   wait_ncc
+//
+// Every other pipeline call needs Idle (most of them a staged pair too) and is refused otherwise; a
+// submit that fails leaves Idle.  run_dlt and run_ncc are their submit followed by their wait.
+// c->staged and c->specU8 describe the staged inputs, not the queue.  The one-shot calls
+// (fm3d_knn2, fm3d_triangulate, fm3d_set_images, ...) do not look at the state: DESIGN.md §2.1.
+enum class PairState { Idle, Full, MemberFront, DltFront, Ncc };
+
+// what an entry point needs of the context before it does anything (require, fm3d_pipeline.cpp)
+enum class Need { Idle, StagedIdle, Full, Dlt, Ncc };
+
+// the timed events of a context, by what they mark on its stream
+enum Ev {
+    EV_LM_START,      // standalone fm3d_optimize_normals: before its launch
+    EV_END,           // the end of whatever was queued last (standalone LM, every pipeline path)
+    EV_FRONT_START,   // front half: before the match
+    EV_MATCH_DONE,    // match + NNDR done (FM3D_STAGE_EVENTS)
+    EV_DLT_DONE,      // triangulation done (FM3D_STAGE_EVENTS)
+    EV_VERIFY_START, EV_VERIFY_END,  // fm3d_pipeline_run(_dlt)_verified: around the verification
+    EV_NORMAL_START, EV_NORMAL_END,  // around the normal stage (LM or NCC scoring)
+    EV_SUBMIT_START,  // a submit, before its inputs' H2D
+    EV_COUNT
+};
+
 }  // namespace fm3d_host
 
 using fm3d_host::DevBuf;
@@ -105,15 +148,14 @@ struct fm3d_ctx {
     DevBuf offsets;
     int nOff = 0, nOffPad = 0;
     // work buffers
-    DevBuf A, B, cqA, ctB, idx, key, fkey, knnOut, cand, flag, matches, count, scanTmp;
-    DevBuf partIdx, partKey;  // per-part top-2 lists of the split matchers
-    DevBuf A8, B8;            // binary rows unpacked to int8 for the MFMA matcher; u8 rows packed from floats
+    DevBuf A, B, knnOut, cand, flag, matches, count, scanTmp;
+    // the k = 2 searches' private buffers: forward, and the cross-check's reverse search (DESIGN.md
+    // §3.1c; allocated only when it runs).  fwd.q8 / fwd.t8 are also the u8 rows packed from floats
+    fm3d_host::KnnWork fwd, rev;
     DevBuf u8Flag;            // launch_f32_pack_u8's "not integer-valued" flag
     // the guided matchers' gate (fm3d_kernels.h EpiGate): query lines (float4) and train (u, v)
     DevBuf gLines, gUV;
     bool gateStaged = false;  // they belong to the staged pair's keypoints under the current g12
-    // the cross-check's reverse search (KnnSide): allocated only when it runs
-    DevBuf rCq, rCt, rA8, rB8, rPartIdx, rPartKey, rPairs, rIdx, rKey, rFkey;
     bool specU8 = false;      // the staged float rows went to the u8 matcher before their flag was read
     // SURF detection / description
     DevBuf sfImg, sfSum, sfDet, sfTr, sfLayers, sfMids, sfCand, sfCount, sfSortTmp, sfFlag, sfPos, sfKp, sfKin, sfSrc,
@@ -136,7 +178,6 @@ struct fm3d_ctx {
     // NCC hypotheses over the pipeline's inliers (fm3d_pipeline_run_ncc)
     DevBuf nccS, nccN, nccB;
     int nccH = 0;
-    DevBuf bPairs;            // the f32 train rows in interleaved pairs
     DevBuf f32Work;           // the bf16 MFMA prefilter's scratch (rows, norms, bounds, candidates)
     int nCU = 0;
     DevBuf kp1, kp2, triPts, triMask, triMask8, pts, srcIdx;
@@ -156,30 +197,26 @@ struct fm3d_ctx {
     HostBuf hA, hB, hK1, hK2, hImg, hTab, hProj, hSmall, hFlag;
     hipEvent_t evStage = nullptr;  // after the last H2D copy from the staging buffers
     hipEvent_t evProj = nullptr;   // after the last H2D copy of the LM constants (hProj)
-    bool pending = false;          // a fm3d_pipeline_submit awaiting fm3d_pipeline_wait
-    // fm3d_pipeline_link: a member's submit queues its front half only; the leader's next submit
-    // queues ONE LM launch over both pairs' points and the member's records behind it
-    fm3d_ctx* linkLeader = nullptr;        // (member) the context that launches its LM
-    std::vector<fm3d_ctx*> linkMembers;    // (leader) the contexts whose pairs join its launches
-    bool frontOnly = false;          // (member) submitted, its LM not queued yet
-    fm3d_record* subOut = nullptr;   // the submitted pair's record destination (device; null: internal)
-    hipEvent_t evFront = nullptr;    // (member) after its front half
-    hipEvent_t evLm = nullptr;       // (leader) after a joint LM launch
-    fm3d_lm_stats subLm{};         // the pending submit's LM launch data
-    bool pendingDlt = false;       // the pending submit is fm3d_pipeline_submit_dlt's front half
-    bool pendingNcc = false;       // the pending submit is fm3d_pipeline_submit_ncc's front half + NCC
-    int nccHPending = 0;           // its hypotheses per point
-    fm3d_record* pendOut = nullptr;  // the device records of the pending / last run
-    // staged pipeline inputs
-    int stNA = 0, stNB = 0, stDim = 0, stType = 0, stDimPad = 0, stQueryOffset = 0;
-    int stK = 0, stP = 0;  // matches and inliers of the last fm3d_pipeline_run_dlt
-    bool stageEv = true;   // the last pipeline_front recorded ev[3] / ev[5] (FM3D_STAGE_EVENTS)
-    int* frontHostCnt = nullptr;  // pipeline_front: the DLT kernel also stores (K, P) here (device pointer)
     int nccP = 0;          // points of the last successful fm3d_pipeline_run_ncc (its score rows)
     bool staged = false;
-    // [0..1] standalone LM, [2..7] pipeline stages ([4] and [9]: around the verification of
-    // fm3d_pipeline_run_verified), [8] submit start, [1] end
-    hipEvent_t ev[10] = {};
+    struct Pipe {  // the staged pipeline's members (fm3d_pipeline.cpp)
+        fm3d_host::PairState state = fm3d_host::PairState::Idle;
+        // staged inputs
+        int nA = 0, nB = 0, dim = 0, type = 0, dimPad = 0, queryOffset = 0;
+        int K = 0, P = 0;      // matches and inliers of the last waited front half
+        bool stageEv = true;   // the last front half recorded EV_MATCH_DONE / EV_DLT_DONE (FM3D_STAGE_EVENTS)
+        fm3d_record* subOut = nullptr;   // the submitted pair's record destination (device; null: internal)
+        fm3d_record* pendOut = nullptr;  // the device records of the pending / last run
+        fm3d_lm_stats subLm{};           // the pending submit's LM launch data
+        int nccHPending = 0;             // the pending NCC scoring's hypotheses per point
+        // fm3d_pipeline_link: a member's submit queues its front half only; the leader's next submit
+        // queues ONE LM launch over both pairs' points and the member's records behind it
+        fm3d_ctx* linkLeader = nullptr;      // (member) the context that launches its LM
+        std::vector<fm3d_ctx*> linkMembers;  // (leader) the contexts whose pairs join its launches
+        hipEvent_t evFront = nullptr;        // (member) after its front half
+        hipEvent_t evLm = nullptr;           // (leader) after a joint LM launch
+    } pipe;
+    hipEvent_t ev[fm3d_host::EV_COUNT] = {};
     std::string err;
 
     fm3d_ctx() = default;
@@ -190,7 +227,7 @@ struct fm3d_ctx {
     // after it, as members.  The stream is idle by then and freeing names no stream, so either
     // order would do: this one keeps the stream a plain member.
     ~fm3d_ctx() {
-        for (hipEvent_t e : {evStage, evProj, evFront, evLm})
+        for (hipEvent_t e : {evStage, evProj, pipe.evFront, pipe.evLm})
             if (e) hipEventDestroy(e);
         for (hipEvent_t e : ev)
             if (e) hipEventDestroy(e);
@@ -205,8 +242,65 @@ inline int fail(fm3d_ctx* c, int code, const std::string& msg) {
     return code;
 }
 
-// the scan scratch and the count word of a compaction over n flags (fm3d_host.cpp)
+// an A/B switch of the environment: on unless its value starts with '0'
+inline bool env_on(const char* name) {
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+}
+
+// ---- fm3d_host.cpp: helpers of more than one translation unit
+// the scan scratch and the count word of a compaction over n flags
 int ensure_scan_tmp(fm3d_ctx* c, int n);
+void install_g12(fm3d_ctx* c, const double g[16]);
+bool good_max_px(double v);  // finite and > 0 (false for NaN)
+// the gate's device inputs from keypoints already on the device (kp1: nA queries, kp2: nB train
+// rows), queued on the context stream
+int make_gate(fm3d_ctx* c, const fm3d_point2f* kp1, int nA, const fm3d_point2f* kp2, int nB, double maxPx,
+              fm3d::EpiGate* g);
+int ensure_offsets(fm3d_ctx* c);
+int upload(fm3d_ctx* c, DevBuf& b, const void* src, size_t bytes);
+int staging_wait(fm3d_ctx* c);
+int upload_pinned(fm3d_ctx* c, DevBuf& dst, HostBuf& h, const void* src, size_t bytes);
+// the look-back state of one fused-compaction launch of nBlocks blocks on c's stream
+int make_lookback(fm3d_ctx* c, int nBlocks, fm3d::LookBack* lb);
+fm3d::TriParams tri_params(fm3d_ctx* c, int K, int queryOffset);
+fm3d::NccParams ncc_params(fm3d_ctx* c, int Hphi, int Htheta, double span);
+int set_images_impl(fm3d_ctx* c, const uint8_t* img1, const uint8_t* img2, int width, int height, int stride,
+                    bool sync = true, bool waitStaging = true);
+
+// ---- fm3d_matching.cpp
+int stage_descriptors(fm3d_ctx* c, const void* descA, int nA, const void* descB, int nB, int dim, int type,
+                      int* effType, int* dimPad, bool waitStaging = true, bool speculate = false);
+// run_match's options.  compactOut / compactCount (the pipeline): NNDR, the parts' merge (int keys)
+// and the stable compaction of the kept matches in one launch; else the NNDR flags and candidates in
+// c->flag / c->cand.  gate (fm3d_kernels.h EpiGate): every type takes its gated kernels.  crossCheck
+// 1 / 2 (with compactOut only): the reverse search over the same rows (and the same
+// gate, transposed), then the NNDR launch's mutual form
+struct MatchOpts {
+    double eps = 0.0;
+    int queryOffset = 0;
+    bool wantKnn = false;
+    fm3d_dmatch* compactOut = nullptr;
+    int* compactCount = nullptr;
+    const fm3d::EpiGate* gate = nullptr;
+    int crossCheck = 0;
+};
+int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, const MatchOpts& o);
+
+// ---- fm3d_lm.cpp
+// One frame pair's points for an LM launch: its context (pyramids c->lvlDesc, pose c->R2/t2,
+// outputs c->lm*, per-pair counters c->pcnt + 16 bytes) and the points (c->pts): P of them, or
+// P their bound when Pdev holds the count on the device (the pipeline: no host sync)
+struct LMSrc {
+    fm3d_ctx* c;
+    int P;
+    const int* Pdev;
+};
+int lm_groups(fm3d_ctx* c, const void* kptr, int slots, long Ptot, long* out);
+int run_lm_multi(fm3d_ctx* c, const LMSrc* src, int nProb, fm3d_lm_stats* stats, hipEvent_t e0, hipEvent_t e1);
+int run_lm(fm3d_ctx* c, int P, const int* Pdev, fm3d_lm_stats* stats, hipEvent_t e0, hipEvent_t e1);
+void fill_lm_cycles(const fm3d_ctx* c, const unsigned long long* cnt, fm3d_lm_stats* st);
+fm3d::Camera lm_camera(const fm3d::Camera& cam);
 
 // fm3d_pipeline_run(_dlt)_verified's middle (fm3d_verify.cpp): the verification of the K matches in
 // c->matches against the staged keypoints, queued on the context stream in c->verWork; the verified

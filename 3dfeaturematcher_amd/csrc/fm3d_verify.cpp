@@ -1,6 +1,6 @@
 // fm3d_verify.cpp -- geometric verification, the host side: fm3d_verify_matches'
 // orchestration (with the refinement rounds of fm3d_verify_matches_refined), the same stage on a staged
-// pipeline pair (verify_staged, for fm3d_pipeline_run(_dlt)_verified in fm3d_host.cpp) and the
+// pipeline pair (verify_staged, for fm3d_pipeline_run(_dlt)_verified in fm3d_pipeline.cpp) and the
 // context-free algebra (sampler, eight-point model, count, normal matrix and refit, pose from E).
 // The arithmetic is include/fm3d_epi8.h's; the kernels are fm3d_verify.hip's.
 #include <hip/hip_runtime.h>
@@ -161,10 +161,10 @@ int fm3d_host::verify_staged(fm3d_ctx* c, const fm3d_verify_opts* o, int K, fm3d
     const size_t oRef = R ? cv.take(fm3d::verify_refine_bytes(M, R)) : 0;
     const size_t oPose = cv.take(fm3d::verify_pose_bytes());
     HIPCHK(c, c->verWork.ensure(cv.off));
-    HIPCHK(c, c->verMatches.ensure((size_t)(c->stNA + 1) * sizeof(fm3d_dmatch)));
+    HIPCHK(c, c->verMatches.ensure((size_t)(c->pipe.nA + 1) * sizeof(fm3d_dmatch)));
     char* const pool = c->verWork.as<char>();
     int* const cnt = c->pcnt.as<int>();
-    HIPCHK(c, hipEventRecord(c->ev[4], st));
+    HIPCHK(c, hipEventRecord(c->ev[EV_VERIFY_START], st));
     fm3d::launch_verify(cam, c->kp1.as<fm3d_point2f>(), c->kp2.as<fm3d_point2f>(), c->matches.as<fm3d_dmatch>(), M, H,
                         o->seed, tau2, c->nCU, (double*)(pool + oXY), (double*)(pool + oMod), (int*)(pool + oCnt),
                         (int*)(pool + oBest), (double*)(pool + oE), (int*)(pool + oFlag), (uint8_t*)(pool + oMask), st,
@@ -184,7 +184,7 @@ int fm3d_host::verify_staged(fm3d_ctx* c, const fm3d_verify_opts* o, int K, fm3d
         fm3d::launch_verify_pose(M, (const double*)(pool + oXY), (const int*)(pool + oFlag), (const int*)(pool + oBest),
                                  (const double*)(pool + oE), pool + oPose, &dCand, &dValid, &dVotes, st);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[9], st));
+    HIPCHK(c, hipEventRecord(c->ev[EV_VERIFY_END], st));
     std::swap(c->matches, c->verMatches);
     struct {
         double cand[fm3d_epi8::kPoseDoubles];
@@ -200,7 +200,7 @@ int fm3d_host::verify_staged(fm3d_ctx* c, const fm3d_verify_opts* o, int K, fm3d
     HIPCHK(c, hipStreamSynchronize(st));
     if (n < 0 || n > M) return fail(c, FM3D_ERR_HIP, "verify: inlier count out of range");
     float ms = 0;
-    hipEventElapsedTime(&ms, c->ev[4], c->ev[9]);
+    hipEventElapsedTime(&ms, c->ev[EV_VERIFY_START], c->ev[EV_VERIFY_END]);
     rep->verify_ms = ms;
     rep->best = best;
     rep->verified = best >= 0 ? n : 0;

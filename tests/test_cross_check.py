@@ -511,3 +511,72 @@ def test_argument_errors(fm3d, synth, ctx):
         assert plain(fresh, vp(a), vp(b), 1) == fm3d.FM3D_OK  # the unguided form needs no pose
     finally:
         fresh.close()
+
+
+NULL_ARG = "null argument"
+NO_POSE = "g12 not set (SingleCameraTriangulator::setg12)"
+BAD_PX = "maxPx must be finite and > 0"
+BAD_MODE = "mode must be 1 (mutual nearest) or 2 (symmetric ratio)"
+# call -> (its arguments after the context, by name; the refusals: {argument: bad value} -> message, in the
+# order the call checks them).  Every refusal is FM3D_ERR_INVALID; "nopose": on a context without g12
+ONE_SHOT = {
+    "fm3d_knn2": ("A nA B nB dim type out",
+                  [({"A": None}, NULL_ARG), ({"B": None}, NULL_ARG), ({"out": None}, NULL_ARG)]),
+    "fm3d_match_nndr": ("A nA B nB dim type eps out cnt",
+                        [({"cnt": None}, NULL_ARG), ({"A": None}, NULL_ARG), ({"B": None}, NULL_ARG),
+                         ({"out": None}, NULL_ARG)]),
+    "fm3d_knn2_guided": ("A nA B nB dim type k1 k2 px out",
+                         [({"A": None}, NULL_ARG), ({"B": None}, NULL_ARG), ({"out": None}, NULL_ARG),
+                          ({"k1": None}, NULL_ARG), ({"k2": None}, NULL_ARG), ({"nopose": 1}, NO_POSE),
+                          ({"nopose": 1, "px": 0.0}, NO_POSE), ({"nopose": 1, "A": None}, NULL_ARG),
+                          ({"px": 0.0}, BAD_PX), ({"px": -1.0}, BAD_PX), ({"px": float("nan")}, BAD_PX),
+                          ({"px": float("inf")}, BAD_PX)]),
+    "fm3d_match_nndr_guided": ("A nA B nB dim type k1 k2 eps px out cnt",
+                               [({"cnt": None}, NULL_ARG), ({"A": None}, NULL_ARG), ({"B": None}, NULL_ARG),
+                                ({"out": None}, NULL_ARG), ({"k1": None}, NULL_ARG), ({"k2": None}, NULL_ARG),
+                                ({"nopose": 1}, NO_POSE), ({"nopose": 1, "px": 0.0}, NO_POSE),
+                                ({"nopose": 1, "k2": None}, NULL_ARG), ({"px": 0.0}, BAD_PX), ({"px": -1.0}, BAD_PX),
+                                ({"px": float("nan")}, BAD_PX), ({"px": float("inf")}, BAD_PX)]),
+    "fm3d_match_mutual": ("A nA B nB dim type eps mode out cnt",
+                          [({"cnt": None}, NULL_ARG), ({"A": None}, NULL_ARG), ({"B": None}, NULL_ARG),
+                           ({"out": None}, NULL_ARG), ({"mode": 0}, BAD_MODE), ({"mode": 3}, BAD_MODE),
+                           ({"mode": 0, "out": None}, NULL_ARG)]),
+    "fm3d_match_mutual_guided": ("A nA B nB dim type k1 k2 eps px mode out cnt",
+                                 [({"cnt": None}, NULL_ARG), ({"A": None}, NULL_ARG), ({"B": None}, NULL_ARG),
+                                  ({"out": None}, NULL_ARG), ({"k1": None}, NULL_ARG), ({"k2": None}, NULL_ARG),
+                                  ({"mode": 0}, BAD_MODE), ({"mode": 3}, BAD_MODE), ({"mode": 0, "k1": None}, NULL_ARG),
+                                  ({"nopose": 1}, NO_POSE), ({"nopose": 1, "mode": 0}, BAD_MODE),
+                                  ({"nopose": 1, "px": 0.0}, NO_POSE), ({"px": 0.0}, BAD_PX), ({"px": -1.0}, BAD_PX),
+                                  ({"px": float("nan")}, BAD_PX), ({"px": float("inf")}, BAD_PX),
+                                  ({"mode": 3, "px": 0.0}, BAD_MODE)]),
+}
+
+
+@pytest.mark.parametrize("call", list(ONE_SHOT))
+def test_one_shot_argument_table(fm3d, synth, ctx, call):
+    """every null / maxPx / mode / missing-pose refusal of the six one-shot matchers, by code and message,
+    and which comes first where two apply"""
+    L = fm3d.lib()
+    a, b = descriptors("u8-128", 4, 6, 1)
+    k1, k2 = keypoints(4, 6)
+    out = np.zeros((4, 2), dtype=fm3d.DMATCH)
+    n = ctypes.c_int(0)
+    vp = lambda x: ctypes.c_void_p(x.ctypes.data)
+    good = {"A": vp(a), "nA": 4, "B": vp(b), "nB": 6, "dim": 128, "type": 1, "k1": vp(k1), "k2": vp(k2), "eps": 0.6,
+            "px": 2.0, "mode": 1, "out": vp(out), "cnt": ctypes.byref(n)}
+    names, refusals = ONE_SHOT[call]
+
+    def run(c, **bad):
+        args = dict(good, **bad)
+        vals = [ctypes.c_double(args[k]) if k in ("eps", "px") else args[k] for k in names.split()]
+        return getattr(L, call)(c.handle, *vals), L.fm3d_last_error(c.handle).decode()
+
+    fresh = make_ctx(fm3d, synth.Camera.reference(WIDTH))  # g12 not set
+    try:
+        assert run(ctx)[0] == fm3d.FM3D_OK
+        for bad, msg in refusals:
+            bad = dict(bad)
+            c = fresh if bad.pop("nopose", 0) else ctx
+            assert run(c, **bad) == (fm3d.ERR_INVALID, msg), (call, bad)
+    finally:
+        fresh.close()

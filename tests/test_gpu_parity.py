@@ -968,7 +968,7 @@ def test_principal_point_zero_and_negative(fm3d, orc, pair, cx, cy):
     top/left edge (the reference has no limit there) -- bit-exact against the oracle, which runs the
     reference's comparisons with the same camera.  The kernel's bit-pattern isPixelGood differs
     from `0 <= u` only for u == -0.0, which only cx == -0.0 can produce; the host hands the kernel
-    +0.0 there (fm3d_host.cpp lm_camera)."""
+    +0.0 there (fm3d_lm.cpp lm_camera)."""
     import dataclasses
     cam = dataclasses.replace(pair.cam, cx=cx, cy=cy)
     q, t, _ = orc.match_nndr(pair.desc1, pair.desc2, orc.U8, 0.55, oracle_threads())
