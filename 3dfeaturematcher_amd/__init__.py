@@ -51,6 +51,8 @@ EXPORTS = (
     "fm3d_pose_from_epipolar",
     "fm3d_verify_matches_refined", "fm3d_epipolar_normal45", "fm3d_epipolar_refit",
     "fm3d_pipeline_run_verified", "fm3d_pipeline_run_dlt_verified",
+    "fm3d_pipeline_submit_verified", "fm3d_pipeline_wait_verified", "fm3d_pipeline_submit_dlt_verified",
+    "fm3d_pipeline_wait_dlt_verified",
 )
 
 # include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
@@ -186,6 +188,20 @@ class VerifyReport(ctypes.Structure):
         return d
 
 
+def _verified_submit_argtypes(L) -> None:
+    """the verified submit / wait calls' signatures (include/fm3d.h); an FM3D_LIB build from before them
+    (tools/verify_stream_bench.py's A/B) simply has none to describe"""
+    vp, ci, pi = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)
+    po, pr, ps = ctypes.POINTER(VerifyOpts), ctypes.POINTER(VerifyReport), ctypes.POINTER(PipelineStats)
+    for name, args in (("fm3d_pipeline_submit_verified", [vp, po, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci]),
+                       ("fm3d_pipeline_wait_verified", [vp, vp, ci, pi, ps, pr]),
+                       ("fm3d_pipeline_submit_dlt_verified", [vp, po]),
+                       ("fm3d_pipeline_wait_dlt_verified", [vp, pi, ps, pr])):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = args
+            getattr(L, name).restype = ctypes.c_int
+
+
 _LIB = None
 
 
@@ -199,6 +215,7 @@ def lib():
         L.fm3d_last_error.restype = ctypes.c_char_p
         L.fm3d_version.restype = ctypes.c_char_p
         L.fm3d_mgpu_last_error.restype = ctypes.c_char_p
+        _verified_submit_argtypes(L)
         _LIB = L
     return _LIB
 
@@ -1158,6 +1175,50 @@ class Pipeline:
         st, rep = PipelineStats(), VerifyReport()
         self.ctx.check(lib().fm3d_pipeline_run_dlt_verified(self.ctx.handle, ctypes.byref(o), ctypes.byref(n),
                                                             ctypes.byref(st), ctypes.byref(rep)))
+        return n.value, st.as_dict(), rep.as_dict()
+
+    def submit_verified(self, desc_a, desc_b, kp1, kp2, img1, img2, max_px, hypotheses: int = 1024, seed: int = 0,
+                        refine: int = 0, binary=False) -> None:
+        """fm3d_pipeline_submit_verified (DESIGN.md §3.1d "Submit / wait"): submit() with the pair's matches
+        verified on the device, in filter mode (the context's pose is kept), queued without waiting: the
+        match count never leaves the device.  The arrays are copied before it returns."""
+        o = self._verify_opts(max_px, hypotheses, seed, refine, False, 1.0)
+        a = np.ascontiguousarray(desc_a)
+        b = np.ascontiguousarray(desc_b)
+        k1 = np.ascontiguousarray(kp1, dtype=np.float32)
+        k2 = np.ascontiguousarray(kp2, dtype=np.float32)
+        i1 = np.ascontiguousarray(img1, dtype=np.uint8)
+        i2 = np.ascontiguousarray(img2, dtype=np.uint8)
+        h, w = i1.shape
+        self.n_queries = a.shape[0]
+        self.ctx.check(lib().fm3d_pipeline_submit_verified(self.ctx.handle, ctypes.byref(o), _vp(a), a.shape[0], _vp(b),
+                                                           b.shape[0], a.shape[1], _desc_type(a, binary), _vp(k1),
+                                                           _vp(k2), _vp(i1), _vp(i2), w, h))
+
+    def wait_verified(self, out: np.ndarray | None = None):
+        """fm3d_pipeline_wait_verified: (survivor records (host), stats dict, report dict) of the pair
+        submit_verified queued, byte for byte run_verified's.  out: as for wait()."""
+        if out is None:
+            out = np.zeros(max(self.n_queries, 1), dtype=RECORD)
+        n = ctypes.c_int(0)
+        st, rep = PipelineStats(), VerifyReport()
+        self.ctx.check(lib().fm3d_pipeline_wait_verified(self.ctx.handle, _vp(out), len(out), ctypes.byref(n),
+                                                         ctypes.byref(st), ctypes.byref(rep)))
+        return out[:n.value], st.as_dict(), rep.as_dict()
+
+    def submit_dlt_verified(self, max_px, hypotheses: int = 1024, seed: int = 0, refine: int = 0) -> None:
+        """fm3d_pipeline_submit_dlt_verified: run_dlt_verified's front half on the staged pair, filter
+        mode, queued on the context stream (returns at once)"""
+        o = self._verify_opts(max_px, hypotheses, seed, refine, False, 1.0)
+        self.ctx.check(lib().fm3d_pipeline_submit_dlt_verified(self.ctx.handle, ctypes.byref(o)))
+
+    def wait_dlt_verified(self):
+        """fm3d_pipeline_wait_dlt_verified: (n_inliers, stats dict, report dict) of the submitted
+        verified front half; dlt_results(stats["matches"], n_inliers) gives its matches and points"""
+        n = ctypes.c_int(0)
+        st, rep = PipelineStats(), VerifyReport()
+        self.ctx.check(lib().fm3d_pipeline_wait_dlt_verified(self.ctx.handle, ctypes.byref(n), ctypes.byref(st),
+                                                             ctypes.byref(rep)))
         return n.value, st.as_dict(), rep.as_dict()
 
     def submit_dlt(self) -> None:

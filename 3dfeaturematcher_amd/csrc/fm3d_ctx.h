@@ -101,15 +101,17 @@ struct KnnWork {
 //   MemberFront  submit on a link member (front half only)    (to Full, see there)
 //   DltFront     submit_dlt, submit_dlt_pair                  wait_dlt
 //   Ncc          submit_ncc                                   wait_ncc
+//   Verified     submit_verified                              wait_verified
+//   DltVerified  submit_dlt_verified                          wait_dlt_verified
 //
 // Every other pipeline call needs Idle (most of them a staged pair too) and is refused otherwise; a
 // submit that fails leaves Idle.  run_dlt and run_ncc are their submit followed by their wait.
 // c->staged and c->specU8 describe the staged inputs, not the queue.  The one-shot calls
 // (fm3d_knn2, fm3d_triangulate, fm3d_set_images, ...) do not look at the state: DESIGN.md §2.1.
-enum class PairState { Idle, Full, MemberFront, DltFront, Ncc };
+enum class PairState { Idle, Full, MemberFront, DltFront, Ncc, Verified, DltVerified };
 
 // what an entry point needs of the context before it does anything (require, fm3d_pipeline.cpp)
-enum class Need { Idle, StagedIdle, Full, Dlt, Ncc };
+enum class Need { Idle, StagedIdle, Full, Dlt, Ncc, Verified, DltVerified };
 
 // the timed events of a context, by what they mark on its stream
 enum Ev {
@@ -118,7 +120,7 @@ enum Ev {
     EV_FRONT_START,   // front half: before the match
     EV_MATCH_DONE,    // match + NNDR done (FM3D_STAGE_EVENTS)
     EV_DLT_DONE,      // triangulation done (FM3D_STAGE_EVENTS)
-    EV_VERIFY_START, EV_VERIFY_END,  // fm3d_pipeline_run(_dlt)_verified: around the verification
+    EV_VERIFY_START, EV_VERIFY_END,  // the verified runs and submits: around the verification
     EV_NORMAL_START, EV_NORMAL_END,  // around the normal stage (LM or NCC scoring)
     EV_SUBMIT_START,  // a submit, before its inputs' H2D
     EV_COUNT
@@ -190,11 +192,13 @@ struct fm3d_ctx {
     DevBuf records, recTmp, recFlag;
     DevBuf lmProj;  // camera-2 projection constants for the LM kernel (fm3d::ProjConst)
     DevBuf pcnt;    // the pipeline's device counts: [0] matches K, [1] inliers P, [2] kept
-    // fm3d_pipeline_run(_dlt)_verified: the verification's working memory (grown on demand, reused across
-    // pairs) and the compaction's output, swapped with `matches` once it holds the verified ones
+    // fm3d_pipeline_run(_dlt)_verified and the verified submits: the verification's working memory (grown
+    // on demand, reused across pairs) and the compaction's output, swapped with `matches` once it holds
+    // the verified ones
     DevBuf verWork, verMatches;
     // pinned staging: descriptors A / B (padded rows), keypoints, images, small tables, results
     HostBuf hA, hB, hK1, hK2, hImg, hTab, hProj, hSmall, hFlag;
+    HostBuf hVer;  // a verified submit's fm3d::VerifySmall, stored by launch_verify_report
     hipEvent_t evStage = nullptr;  // after the last H2D copy from the staging buffers
     hipEvent_t evProj = nullptr;   // after the last H2D copy of the LM constants (hProj)
     int nccP = 0;          // points of the last successful fm3d_pipeline_run_ncc (its score rows)
@@ -310,6 +314,15 @@ fm3d::Camera lm_camera(const fm3d::Camera& cam);
 // installed).  K >= 8.
 int verify_staged(fm3d_ctx* c, const fm3d_verify_opts* o, int K, fm3d_verify_report* rep, bool* havePose,
                   double g12[16]);
+// The same stage for the verified submits, in filter mode (o->poseFromModel == 0), behind a queued match
+// half and without a host wait: the device-count launch forms, sized by the staged nA and reading the
+// match count where the match stage left it, c->pcnt[0].  The compaction puts the verified count there
+// and launch_verify_report stores the match count, the verified count, best, the adopted rounds and E
+// to c->hVer for the wait (verify_report).  No model: every flag is 0 and so is the verified count.
+int verify_staged_queue(fm3d_ctx* c, const fm3d_verify_opts* o);
+// after the stream ran verify_staged_queue: rep from c->hVer, the context's pose and the events.
+// FM3D_ERR_HIP for a count outside [0, nA].
+int verify_report(fm3d_ctx* c, fm3d_verify_report* rep);
 
 }  // namespace fm3d_host
 

@@ -317,8 +317,9 @@ void launch_sift_desc(const float* gp, const SiftLevel* GL, int L, int firstOcta
 // ---------------- compaction ----------------
 // out[k] = in[i] for flag[i] != 0, stable; *count (device) = number kept.  tmp >= scan_tmp_bytes(n).
 size_t scan_tmp_bytes(int n);
+// nDev (may be null): the item count on the device, n its bound; a word of its own, never `count`
 void launch_compact_dmatch(const fm3d_dmatch* in, const int* flag, int n, fm3d_dmatch* out, int* count, void* tmp,
-                           hipStream_t s);
+                           hipStream_t s, const int* nDev = nullptr);
 // nDev (may be null): the item count on the device, n its bound (device-sized launches: no host sync)
 void launch_compact_points(const double* in, const int* flag, int n, const int* nDev, double* out, int* count,
                            int* srcIndex, void* tmp, hipStream_t s);
@@ -332,9 +333,14 @@ int verify_pad(int M);                    // M rounded up to whole tiles
 // hypotheses (models H x 9, count H: -1 for an invalid one), their scores, the best (best, E[9]: -1 and
 // zeros when none is valid) and its inlier mask (flag M ints for the compaction, mask M bytes).
 // M >= 8, 1 <= H <= kVerifyMaxHyps, every match index inside its keypoint array.
+// The device-count form (Mdev != null, as TriParams::Kdev): M >= 1 is a bound and *Mdev, any value in
+// 0 .. M, the count.  Every grid and every buffer is sized by M as above (the planes' stride is
+// verify_pad(M)); the kernels read *Mdev; best, E, count and models come out as those of a call with
+// M = *Mdev, bit for bit, flag and mask hold *Mdev entries, and *Mdev < 8 gives best = -1.
 void launch_verify(const Camera& cam, const fm3d_point2f* kp1, const fm3d_point2f* kp2, const fm3d_dmatch* matches,
                    int M, int H, unsigned long long seed, double tau2, int nCU, double* xy, double* models, int* count,
-                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s, bool withMask = true);
+                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s, bool withMask = true,
+                   const int* Mdev = nullptr);
 // The refinement after launch_verify(..., withMask = false): `rounds` (1 .. 16) refits of E on its own
 // inliers, each adopted iff valid and no worse in count, all queued on s without a host sync, then the
 // mask of the final E.  work: verify_refine_bytes(M, rounds), 8-byte aligned; the three outputs point
@@ -342,7 +348,16 @@ void launch_verify(const Camera& cam, const fm3d_point2f* kp1, const fm3d_point2
 size_t verify_refine_bytes(int M, int rounds);
 void launch_verify_refine(int M, int rounds, double tau2, const double* xy, const int* count, const int* best,
                           double* E, void* work, int* flag, uint8_t* mask, int** roundCounts, double** roundModels,
-                          int** adopted, hipStream_t s);
+                          int** adopted, hipStream_t s, const int* Mdev = nullptr);
+// The few values a caller that never waited for the verification reads afterwards: launch_verify_report
+// stores them to page-locked memory (host: a device pointer to it) behind the compaction, whose count
+// `verified` names; adopted may be null (no rounds: 0).
+struct VerifySmall {
+    int32_t matches, verified, best, adopted;
+    double E[9];
+};
+void launch_verify_report(const int* Mdev, const int* best, const double* E, const int* adopted, const int* verified,
+                          VerifySmall* host, hipStream_t s);
 // The pose stage behind the final model (launch_verify with its mask, or launch_verify_refine): the two
 // rotations and u_2 of E (fm3d_epi8::pose_candidates; cand: 21 doubles, R[0], R[1], u_2), *valid = 0
 // when best < 0 or E has no decomposition, and votes[4]: per candidate the matches with flag != 0 that

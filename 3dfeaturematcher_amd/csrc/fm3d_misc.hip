@@ -530,8 +530,8 @@ void launch_epipolar_setup(const Camera& cam, const double E[9], const fm3d_poin
 size_t scan_tmp_bytes(int n) { return sizeof(int) * ((size_t)(n + kScanBlock - 1) / kScanBlock + 16); }
 
 void launch_compact_dmatch(const fm3d_dmatch* in, const int* flag, int n, fm3d_dmatch* out, int* count, void* tmp,
-                           hipStream_t s) {
-    compact<fm3d_dmatch>(in, flag, n, nullptr, out, count, nullptr, tmp, s);
+                           hipStream_t s, const int* nDev) {
+    compact<fm3d_dmatch>(in, flag, n, nDev, out, count, nullptr, tmp, s);
 }
 
 void launch_compact_points(const double* in, const int* flag, int n, const int* nDev, double* out, int* count,

@@ -1,7 +1,8 @@
 // fm3d_pipeline.cpp -- the staged pipeline: one frame pair's inputs resident in HBM and the whole
-// path, its front half alone, the verified forms or the NCC scoring queued on the context stream
-// (fm3d_pipeline_*), and the multi-GPU host's entry points (fm3d_internal_*, fm3d_internal.h).  What
-// is queued and not yet waited for is c->pipe.state (fm3d_ctx.h PairState): see require().
+// path, its front half alone, the verified forms (synchronous, and as submit / wait) or the NCC scoring
+// queued on the context stream (fm3d_pipeline_*), and the multi-GPU host's entry points
+// (fm3d_internal_*, fm3d_internal.h).  What is queued and not yet waited for is c->pipe.state
+// (fm3d_ctx.h PairState): see require().
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -19,6 +20,17 @@ int require(fm3d_ctx* c, Need need) {
     if (need == Need::StagedIdle && (!c || !c->staged)) return fail(c, FM3D_ERR_INVALID, "fm3d_pipeline_upload not called");
     if (!c) return FM3D_ERR_INVALID;
     const PairState s = c->pipe.state;
+    // a verified pair has waits of its own, and they serve nothing else
+    if (need != Need::StagedIdle && need != Need::Idle) {
+        if (s == PairState::Verified && need != Need::Verified)
+            return fail(c, FM3D_ERR_INVALID, "a verified frame pair is pending: fm3d_pipeline_wait_verified");
+        if (s == PairState::DltVerified && need != Need::DltVerified)
+            return fail(c, FM3D_ERR_INVALID, "a verified front half is pending: fm3d_pipeline_wait_dlt_verified");
+    }
+    if (need == Need::Verified && s != PairState::Verified)
+        return fail(c, FM3D_ERR_INVALID, "no verified frame pair submitted (fm3d_pipeline_submit_verified)");
+    if (need == Need::DltVerified && s != PairState::DltVerified)
+        return fail(c, FM3D_ERR_INVALID, "no verified front half submitted (fm3d_pipeline_submit_dlt_verified)");
     if ((need == Need::StagedIdle || need == Need::Idle) && s != PairState::Idle)
         return fail(c, FM3D_ERR_INVALID, "a submitted frame pair is pending: fm3d_pipeline_wait first");
     if (need == Need::Full) {
@@ -361,10 +373,11 @@ int redo_float_front(fm3d_ctx* c) {
     return FM3D_OK;
 }
 
-// fm3d_pipeline_run(_dlt)_verified's argument rules, before any launch
-int check_verified(fm3d_ctx* c, const fm3d_verify_opts* o, const fm3d_verify_report* rep) {
-    if (!c || !o || !rep) return fail(c, FM3D_ERR_INVALID, "null argument");
-    if (int r = require(c, Need::StagedIdle)) return r;
+// fm3d_pipeline_run(_dlt)_verified's argument rules, before any launch (haveRep: the call's report is not
+// null, or it takes none; need: StagedIdle for a call on the staged pair, Idle for one that stages its own)
+int check_verified(fm3d_ctx* c, const fm3d_verify_opts* o, bool haveRep, Need need = Need::StagedIdle) {
+    if (!c || !o || !haveRep) return fail(c, FM3D_ERR_INVALID, "null argument");
+    if (int r = require(c, need)) return r;
     if (o->hypotheses < 1) return fail(c, FM3D_ERR_INVALID, "hypotheses must be >= 1");
     if (o->refineIters < 0 || o->refineIters > 16) return fail(c, FM3D_ERR_INVALID, "refineIters must be in 0 .. 16");
     if (!good_max_px(o->maxPx)) return fail(c, FM3D_ERR_INVALID, "maxPx must be finite and > 0");
@@ -376,7 +389,7 @@ int check_verified(fm3d_ctx* c, const fm3d_verify_opts* o, const fm3d_verify_rep
             return fail(c, FM3D_ERR_INVALID,
                         "poseFromModel with guidedMatchPx > 0: the gate needs the pose this call is about to find");
     }
-    if (c->pipe.queryOffset != 0)
+    if (need == Need::StagedIdle && c->pipe.queryOffset != 0)
         return fail(c, FM3D_ERR_UNSUPPORTED, "a staged queryOffset != 0: a share sees only its own matches");
     if (o->hypotheses > fm3d::kVerifyMaxHyps) return fail(c, FM3D_ERR_UNSUPPORTED, "more than 2^20 hypotheses");
     return FM3D_OK;
@@ -390,7 +403,7 @@ int front_verified(fm3d_ctx* c, const fm3d_verify_opts* o, fm3d_verify_report* r
                    fm3d_pipeline_stats* stats, bool* go) {
     int r;
     *go = false;
-    if ((r = check_verified(c, o, rep))) return r;
+    if ((r = check_verified(c, o, rep != nullptr))) return r;
     hipSetDevice(c->device);
     std::memset(rep, 0, sizeof(*rep));
     rep->best = -1;
@@ -422,6 +435,31 @@ int front_verified(fm3d_ctx* c, const fm3d_verify_opts* o, fm3d_verify_report* r
         if (stats) stats_head(c, 0, 0, false, stats);  // no counts, no times
     }
     return FM3D_OK;
+}
+
+// the verified submits' rules on top: filter mode only, and no joined LM launches
+int check_verified_submit(fm3d_ctx* c, const fm3d_verify_opts* o, Need need) {
+    if (int r = check_verified(c, o, true, need)) return r;
+    if (o->poseFromModel)
+        return fail(c, FM3D_ERR_UNSUPPORTED,
+                    "poseFromModel = 1 has no submit / wait form: the synchronous fm3d_pipeline_run_verified / "
+                    "fm3d_pipeline_run_dlt_verified serve it");
+    if (c->pipe.linkLeader || !c->pipe.linkMembers.empty())
+        return fail(c, FM3D_ERR_UNSUPPORTED, "a linked context (fm3d_pipeline_link): verified pairs join no LM launch");
+    return FM3D_OK;
+}
+
+// The verified path on the staged inputs, queued on the context stream: the match half, the
+// verification on the device's counts with its compaction and the buffer swap (verify_staged_queue),
+// then the DLT half with its counts to page-locked memory (front only) or the DLT, the LM, the records
+// and the small D2H.  Nothing here waits for the device; with no model every later stage sees 0 items.
+int enqueue_verified(fm3d_ctx* c, const fm3d_verify_opts* o, bool frontOnly) {
+    int r;
+    if ((r = front_match(c))) return r;
+    if ((r = verify_staged_queue(c, o))) return r;
+    if (frontOnly) return front_with_counts(c, false);
+    if ((r = front_dlt(c, nullptr))) return r;
+    return enqueue_normals(c, nullptr, &c->pipe.subLm);
 }
 
 }  // namespace
@@ -539,6 +577,59 @@ int fm3d_pipeline_run_dlt_verified(fm3d_ctx* c, const fm3d_verify_opts* o, int* 
     if ((r = front_verified(c, o, rep, nInliers, stats, &go)) || !go) return r;
     if ((r = front_with_counts(c, false))) return r;
     HIPCHK(c, hipEventSynchronize(c->ev[EV_END]));
+    report_front_counts(c, nInliers, stats);
+    return FM3D_OK;
+}
+
+int fm3d_pipeline_submit_verified(fm3d_ctx* c, const fm3d_verify_opts* o, const void* descA, int nA, const void* descB,
+                                  int nB, int dim, int type, const fm3d_point2f* kpts1, const fm3d_point2f* kpts2,
+                                  const uint8_t* img1, const uint8_t* img2, int width, int height) {
+    int r;
+    if ((r = check_verified_submit(c, o, Need::Idle))) return r;
+    hipSetDevice(c->device);
+    HIPCHK(c, hipEventRecord(c->ev[EV_SUBMIT_START], c->stream));
+    if ((r = stage_pipeline(c, {descA, nA, descB, nB, dim, type, kpts1, kpts2, img1, img2, width, height, 0}))) return r;
+    c->pipe.subLm = fm3d_lm_stats{};
+    c->pipe.subOut = nullptr;
+    if ((r = enqueue_verified(c, o, false))) return r;
+    c->pipe.state = PairState::Verified;
+    return FM3D_OK;
+}
+
+int fm3d_pipeline_wait_verified(fm3d_ctx* c, fm3d_record* out, int cap, int* nKept, fm3d_pipeline_stats* stats,
+                                fm3d_verify_report* rep) {
+    int r;
+    if (!c || !rep) return fail(c, FM3D_ERR_INVALID, "null argument");
+    if ((r = require(c, Need::Verified))) return r;
+    hipSetDevice(c->device);
+    c->pipe.state = PairState::Idle;
+    int kept = 0;
+    if ((r = finalize_full(c, c->pipe.subLm, c->ev[EV_SUBMIT_START], true, &kept, stats))) return r;
+    if ((r = verify_report(c, rep))) return r;
+    if (out && kept > cap) return fail(c, FM3D_ERR_INVALID, "record buffer too small");
+    if (out && kept)
+        HIPCHK(c, hipMemcpy(out, c->pipe.pendOut, (size_t)kept * sizeof(fm3d_record), hipMemcpyDeviceToHost));
+    if (nKept) *nKept = kept;
+    return FM3D_OK;
+}
+
+int fm3d_pipeline_submit_dlt_verified(fm3d_ctx* c, const fm3d_verify_opts* o) {
+    int r;
+    if ((r = check_verified_submit(c, o, Need::StagedIdle))) return r;
+    hipSetDevice(c->device);
+    if ((r = enqueue_verified(c, o, true))) return r;
+    c->pipe.state = PairState::DltVerified;
+    return FM3D_OK;
+}
+
+int fm3d_pipeline_wait_dlt_verified(fm3d_ctx* c, int* nInliers, fm3d_pipeline_stats* stats, fm3d_verify_report* rep) {
+    int r;
+    if (!c || !rep) return fail(c, FM3D_ERR_INVALID, "null argument");
+    if ((r = require(c, Need::DltVerified))) return r;
+    hipSetDevice(c->device);
+    c->pipe.state = PairState::Idle;
+    HIPCHK(c, hipEventSynchronize(c->ev[EV_END]));
+    if ((r = verify_report(c, rep))) return r;
     report_front_counts(c, nInliers, stats);
     return FM3D_OK;
 }

@@ -216,6 +216,71 @@ int fm3d_host::verify_staged(fm3d_ctx* c, const fm3d_verify_opts* o, int K, fm3d
     return FM3D_OK;
 }
 
+int fm3d_host::verify_staged_queue(fm3d_ctx* c, const fm3d_verify_opts* o) {
+    const int Mcap = c->pipe.nA > 0 ? c->pipe.nA : 1, H = o->hypotheses, R = o->refineIters;
+    const fm3d::Camera& cam = c->cam;
+    const double tau = o->maxPx * 2.0 / (cam.fx + cam.fy);
+    const double tau2 = tau * tau;
+    hipStream_t st = c->stream;
+    // verify_staged's carving by the bound, and the match count's own word: the compaction reads it while
+    // it writes c->pcnt[0]
+    const int Mpad = fm3d::verify_pad(Mcap);
+    Carver cv;
+    const size_t oK = cv.take(sizeof(int)), oXY = cv.take((size_t)4 * Mpad * sizeof(double));
+    const size_t oMod = cv.take((size_t)H * 9 * sizeof(double)), oCnt = cv.take((size_t)H * sizeof(int));
+    const size_t oBest = cv.take(sizeof(int)), oE = cv.take(9 * sizeof(double));
+    const size_t oFlag = cv.take((size_t)Mcap * sizeof(int)), oMask = cv.take((size_t)Mcap);
+    const size_t oRef = R ? cv.take(fm3d::verify_refine_bytes(Mcap, R)) : 0;
+    HIPCHK(c, c->verWork.ensure(cv.off));
+    HIPCHK(c, c->verMatches.ensure((size_t)(c->pipe.nA + 1) * sizeof(fm3d_dmatch)));
+    HIPCHK(c, c->hVer.ensure(sizeof(fm3d::VerifySmall)));
+    fm3d::VerifySmall* hv = c->hVer.as<fm3d::VerifySmall>();
+    *hv = fm3d::VerifySmall{-1, -1, -1, 0, {0., 0., 0., 0., 0., 0., 0., 0., 0.}};  // until the kernel's stores arrive
+    void* dhv = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer(&dhv, hv, 0));
+    char* const pool = c->verWork.as<char>();
+    int* const cnt = c->pcnt.as<int>();
+    const int* const Mdev = (const int*)(pool + oK);
+    HIPCHK(c, hipEventRecord(c->ev[EV_VERIFY_START], st));
+    HIPCHK(c, hipMemcpyAsync(pool + oK, cnt + 0, sizeof(int), hipMemcpyDeviceToDevice, st));
+    fm3d::launch_verify(cam, c->kp1.as<fm3d_point2f>(), c->kp2.as<fm3d_point2f>(), c->matches.as<fm3d_dmatch>(), Mcap,
+                        H, o->seed, tau2, c->nCU, (double*)(pool + oXY), (double*)(pool + oMod), (int*)(pool + oCnt),
+                        (int*)(pool + oBest), (double*)(pool + oE), (int*)(pool + oFlag), (uint8_t*)(pool + oMask), st,
+                        R == 0, Mdev);
+    int *dRoundCounts = nullptr, *dAdopted = nullptr;
+    double* dRoundModels = nullptr;
+    if (R)
+        fm3d::launch_verify_refine(Mcap, R, tau2, (const double*)(pool + oXY), (const int*)(pool + oCnt),
+                                   (const int*)(pool + oBest), (double*)(pool + oE), pool + oRef, (int*)(pool + oFlag),
+                                   (uint8_t*)(pool + oMask), &dRoundCounts, &dRoundModels, &dAdopted, st, Mdev);
+    // the verified matches and their count where the DLT reads them (c->scanTmp holds stNA >= Mcap items)
+    fm3d::launch_compact_dmatch(c->matches.as<fm3d_dmatch>(), (const int*)(pool + oFlag), Mcap,
+                                c->verMatches.as<fm3d_dmatch>(), cnt + 0, c->scanTmp.p, st, Mdev);
+    fm3d::launch_verify_report(Mdev, (const int*)(pool + oBest), (const double*)(pool + oE), dAdopted, cnt + 0,
+                               (fm3d::VerifySmall*)dhv, st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev[EV_VERIFY_END], st));
+    std::swap(c->matches, c->verMatches);
+    return FM3D_OK;
+}
+
+int fm3d_host::verify_report(fm3d_ctx* c, fm3d_verify_report* rep) {
+    const fm3d::VerifySmall hv = *c->hVer.as<fm3d::VerifySmall>();
+    if (hv.matches < 0 || hv.matches > c->pipe.nA) return fail(c, FM3D_ERR_HIP, "match count out of range");
+    if (hv.verified < 0 || hv.verified > hv.matches) return fail(c, FM3D_ERR_HIP, "verify: inlier count out of range");
+    std::memset(rep, 0, sizeof(*rep));
+    rep->matches = hv.matches;
+    rep->best = hv.best;
+    rep->verified = hv.best >= 0 ? hv.verified : 0;
+    rep->roundsAdopted = hv.adopted;
+    std::memcpy(rep->E, hv.E, sizeof(rep->E));
+    std::memcpy(rep->g12, c->g12, sizeof(rep->g12));
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev[EV_VERIFY_START], c->ev[EV_VERIFY_END]);
+    rep->verify_ms = ms;
+    return FM3D_OK;
+}
+
 int fm3d_verify_matches(fm3d_ctx* c, const fm3d_point2f* kpts1, int n1, const fm3d_point2f* kpts2, int n2,
                         const fm3d_dmatch* matches, int nMatches, int hypotheses, double maxPx, uint64_t seed,
                         double E[9], uint8_t* inlierMask, fm3d_dmatch* inliers, int* nInliers, int* best,

@@ -18,13 +18,31 @@ constexpr int kScorePer = 4;        // matches a lane keeps in registers
 constexpr int kScoreHyps = 64;      // most hypotheses one workgroup scores
 static_assert(kScoreThreads * kScorePer == kVerifyTile, "a scoring workgroup covers one tile of matches");
 
-// xy: four planes of Mpad doubles (x1, y1, x2, y2); the pad holds NaN, which no model accepts
+// M: the match count, or its bound when Mdev holds the count on the device (the device-count forms:
+// every grid and the planes' stride Mpad are sized by the bound).  One address for every thread, so
+// a scalar load; a count outside [0, M] is clamped, so nothing is indexed past the bound.
+__device__ __forceinline__ int dev_matches(const int* __restrict__ Mdev, int M) {
+    if (!Mdev) return M;
+    const int d = *Mdev;
+    return d < 0 ? 0 : (d < M ? d : M);
+}
+
+// a tile of 1,024 slots that lies entirely past the device count holds only NaN: it adds nothing to a
+// count, and the solve never reads its partials.  The same for every thread of the workgroup.
+__device__ __forceinline__ bool tile_past_count(const int* __restrict__ Mdev, int Mpad) {
+    return Mdev && (long long)blockIdx.x * kVerifyTile >= dev_matches(Mdev, Mpad);
+}
+
+// xy: four planes of Mpad doubles (x1, y1, x2, y2); the pad -- every slot from the count to Mpad, whole
+// tiles of it with a device count -- holds NaN, which no model accepts
 __global__ __launch_bounds__(256) void verify_coords_kernel(Camera cam, const fm3d_point2f* __restrict__ kp1,
                                                             const fm3d_point2f* __restrict__ kp2,
-                                                            const fm3d_dmatch* __restrict__ matches, int M, int Mpad,
+                                                            const fm3d_dmatch* __restrict__ matches, int M,
+                                                            const int* __restrict__ Mdev, int Mpad,
                                                             double* __restrict__ xy) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Mpad) return;
+    M = dev_matches(Mdev, M);
     double x1, y1, x2, y2;
     x1 = y1 = x2 = y2 = __builtin_nan("");
     if (i < M) {
@@ -47,13 +65,15 @@ struct LdsMat {
     __device__ double& operator()(int r, int c) { return p[(r * 9 + c) * kHypThreads]; }
 };
 
-__global__ __launch_bounds__(kHypThreads) void verify_hypothesis_kernel(const double* __restrict__ xy, int M, int Mpad,
+__global__ __launch_bounds__(kHypThreads) void verify_hypothesis_kernel(const double* __restrict__ xy, int M,
+                                                                        const int* __restrict__ Mdev, int Mpad,
                                                                         int H, unsigned long long seed,
                                                                         double* __restrict__ models,
                                                                         int* __restrict__ count) {
     __shared__ double sA[72 * kHypThreads];
     const int h = blockIdx.x * kHypThreads + threadIdx.x;
     if (h >= H) return;
+    M = dev_matches(Mdev, M);  // fewer than 8: no sample exists, every hypothesis is invalid
     LdsMat A{sA + threadIdx.x};
     int idx[8];
     double E[9], e[9];
@@ -79,10 +99,12 @@ __global__ __launch_bounds__(kHypThreads) void verify_hypothesis_kernel(const do
 // loads); a wave counts with ballots, the workgroup adds its four waves in LDS, and one atomicAdd per
 // (workgroup, hypothesis) with a non-zero count goes to count[h] -- integers, exact in any order.  An
 // invalid hypothesis is the zero model: den == 0 accepts nothing, its count stays -1.
-__global__ __launch_bounds__(kScoreThreads) void verify_score_kernel(const double* __restrict__ xy, int Mpad,
+__global__ __launch_bounds__(kScoreThreads) void verify_score_kernel(const double* __restrict__ xy,
+                                                                     const int* __restrict__ Mdev, int Mpad,
                                                                      const double* __restrict__ models, int H, int hc,
                                                                      double tau2, int* __restrict__ count) {
     __shared__ int sCnt[kScoreThreads / 64][kScoreHyps];
+    if (tile_past_count(Mdev, Mpad)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double x1[kScorePer], y1[kScorePer], x2[kScorePer], y2[kScorePer];
 #pragma unroll
@@ -149,12 +171,13 @@ __global__ __launch_bounds__(256) void verify_argmax_kernel(const int* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void verify_mask_kernel(const double* __restrict__ xy, int M, int Mpad,
+__global__ __launch_bounds__(256) void verify_mask_kernel(const double* __restrict__ xy, int M,
+                                                          const int* __restrict__ Mdev, int Mpad,
                                                           const int* __restrict__ best, const double* __restrict__ Eb,
                                                           double tau2, int* __restrict__ flag,
                                                           uint8_t* __restrict__ mask) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
+    if (i >= dev_matches(Mdev, M)) return;
     double E[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) E[k] = Eb[k];
@@ -195,12 +218,14 @@ __global__ __launch_bounds__(64) void verify_refine_init_kernel(const int* __res
 // k * 256 + tid, evaluates the predicate itself and forms leaf4 of their products; the wave's 64
 // leaves go through an xor butterfly (strides 1 .. 32: the balanced tree's bits in every lane, IEEE
 // addition being commutative), the four waves through LDS as (w0 + w1) + (w2 + w3).
-__global__ __launch_bounds__(kScoreThreads) void verify_normal_kernel(const double* __restrict__ xy, int Mpad,
+__global__ __launch_bounds__(kScoreThreads) void verify_normal_kernel(const double* __restrict__ xy,
+                                                                      const int* __restrict__ Mdev, int Mpad,
                                                                       const double* __restrict__ Ecur, double tau2,
                                                                       const int* __restrict__ st,
                                                                       double* __restrict__ partial) {
     __shared__ double sW[kScoreThreads / 64][fm3d_epi8::kPairs];
     if (st[kStDone]) return;
+    if (tile_past_count(Mdev, Mpad)) return;  // its partials stay what they were: the solve stops before them
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double E[9];
 #pragma unroll
@@ -245,16 +270,20 @@ struct WaveTeam {
     __device__ void sync() const { __syncthreads(); }
 };
 
-// One workgroup of one wave: 45 threads add the tile partials in tile order from +0.0; every lane runs
+// One workgroup of one wave: 45 threads add the tile partials in tile order from +0.0 -- with a device
+// count only the ceil(count / 1024) leading tiles', the ones the normal kernel wrote for this pair, so
+// the sums are those of a run sized by the count and no older pair's partial is read; every lane runs
 // the Jacobi iteration on the S and V in LDS, lane k updating row k of a rotation; thread 0 projects.
 // cand: E' (zero when invalid); st: the valid flag and the candidate's count, 0 for the count kernel
 // to add to, -1 when there is nothing to count.
 __global__ __launch_bounds__(64) void verify_solve_kernel(const double* __restrict__ partial, int tiles,
-                                                          int* __restrict__ st, double* __restrict__ cand) {
+                                                          const int* __restrict__ Mdev, int* __restrict__ st,
+                                                          double* __restrict__ cand) {
     __shared__ double sN[fm3d_epi8::kPairs], sS[81], sV[81], sE[9];
     __shared__ int sOk;
     const int tid = threadIdx.x;
     if (st[kStDone]) return;
+    if (Mdev) tiles = (dev_matches(Mdev, tiles * kVerifyTile) + kVerifyTile - 1) / kVerifyTile;
     if (tid < fm3d_epi8::kPairs) {
         double s = 0.;
         for (int t = 0; t < tiles; t++) s = s + partial[(size_t)t * fm3d_epi8::kPairs + tid];
@@ -278,11 +307,13 @@ __global__ __launch_bounds__(64) void verify_solve_kernel(const double* __restri
 
 // c' of a valid E': verify_score_kernel's count for one model, behind the rounds' flags (integers:
 // the atomicAdd per workgroup is exact in any order)
-__global__ __launch_bounds__(kScoreThreads) void verify_count_kernel(const double* __restrict__ xy, int Mpad,
+__global__ __launch_bounds__(kScoreThreads) void verify_count_kernel(const double* __restrict__ xy,
+                                                                     const int* __restrict__ Mdev, int Mpad,
                                                                      const double* __restrict__ cand, double tau2,
                                                                      int* __restrict__ st) {
     __shared__ int sCnt[kScoreThreads / 64];
     if (st[kStDone] || !st[kStValid]) return;
+    if (tile_past_count(Mdev, Mpad)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double E[9];
 #pragma unroll
@@ -404,7 +435,30 @@ __global__ __launch_bounds__(kScoreThreads) void verify_pose_vote_kernel(const d
     }
 }
 
+// What the host reads of a verification it never waited for, stored to page-locked memory (host: a
+// device pointer to it) with system-scope stores, as the DLT kernel stores its counts: a caller that
+// waits for the stream reads it without a copy launch.  One wave; Mdev holds the match stage's count,
+// verified the compaction's.
+__global__ __launch_bounds__(64) void verify_report_kernel(const int* __restrict__ Mdev, const int* __restrict__ best,
+                                                           const double* __restrict__ E,
+                                                           const int* __restrict__ adopted,
+                                                           const int* __restrict__ verified, VerifySmall* host) {
+    const int tid = threadIdx.x;
+    if (tid < 9) __hip_atomic_store(&host->E[tid], E[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (tid == 0) {
+        __hip_atomic_store(&host->matches, *Mdev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host->verified, *verified, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host->best, *best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host->adopted, adopted ? *adopted : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 }  // namespace
+
+void launch_verify_report(const int* Mdev, const int* best, const double* E, const int* adopted, const int* verified,
+                          VerifySmall* host, hipStream_t s) {
+    verify_report_kernel<<<1, 64, 0, s>>>(Mdev, best, E, adopted, verified, host);
+}
 
 size_t verify_pose_bytes() { return fm3d_epi8::kPoseDoubles * sizeof(double) + 8 * sizeof(int); }
 
@@ -428,7 +482,7 @@ size_t verify_refine_bytes(int M, int rounds) {
 
 void launch_verify_refine(int M, int rounds, double tau2, const double* xy, const int* count, const int* best,
                           double* E, void* work, int* flag, uint8_t* mask, int** roundCounts, double** roundModels,
-                          int** adopted, hipStream_t s) {
+                          int** adopted, hipStream_t s, const int* Mdev) {
     const int Mpad = verify_pad(M), tiles = Mpad / kVerifyTile;
     double* partial = (double*)work;
     double* cand = partial + (size_t)tiles * fm3d_epi8::kPairs;
@@ -437,12 +491,12 @@ void launch_verify_refine(int M, int rounds, double tau2, const double* xy, cons
     int* rc = st + kStWords;
     verify_refine_init_kernel<<<1, 64, 0, s>>>(best, count, rounds, st, rc, rm);
     for (int r = 0; r < rounds; r++) {
-        verify_normal_kernel<<<tiles, kScoreThreads, 0, s>>>(xy, Mpad, E, tau2, st, partial);
-        verify_solve_kernel<<<1, 64, 0, s>>>(partial, tiles, st, cand);
-        verify_count_kernel<<<tiles, kScoreThreads, 0, s>>>(xy, Mpad, cand, tau2, st);
+        verify_normal_kernel<<<tiles, kScoreThreads, 0, s>>>(xy, Mdev, Mpad, E, tau2, st, partial);
+        verify_solve_kernel<<<1, 64, 0, s>>>(partial, tiles, Mdev, st, cand);
+        verify_count_kernel<<<tiles, kScoreThreads, 0, s>>>(xy, Mdev, Mpad, cand, tau2, st);
         verify_adopt_kernel<<<1, 64, 0, s>>>(r, st, cand, E, rc, rm);
     }
-    verify_mask_kernel<<<(M + 255) / 256, 256, 0, s>>>(xy, M, Mpad, best, E, tau2, flag, mask);
+    verify_mask_kernel<<<(M + 255) / 256, 256, 0, s>>>(xy, M, Mdev, Mpad, best, E, tau2, flag, mask);
     *roundCounts = rc;
     *roundModels = rm;
     *adopted = st + kStAdopted;
@@ -452,20 +506,21 @@ int verify_pad(int M) { return (int)(((long long)M + kVerifyTile - 1) / kVerifyT
 
 void launch_verify(const Camera& cam, const fm3d_point2f* kp1, const fm3d_point2f* kp2, const fm3d_dmatch* matches,
                    int M, int H, unsigned long long seed, double tau2, int nCU, double* xy, double* models, int* count,
-                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s, bool withMask) {
+                   int* best, double* E, int* flag, uint8_t* mask, hipStream_t s, bool withMask, const int* Mdev) {
     const int Mpad = verify_pad(M);
-    verify_coords_kernel<<<(Mpad + 255) / 256, 256, 0, s>>>(cam, kp1, kp2, matches, M, Mpad, xy);
-    verify_hypothesis_kernel<<<(H + kHypThreads - 1) / kHypThreads, kHypThreads, 0, s>>>(xy, M, Mpad, H, seed, models,
-                                                                                       count);
+    verify_coords_kernel<<<(Mpad + 255) / 256, 256, 0, s>>>(cam, kp1, kp2, matches, M, Mdev, Mpad, xy);
+    verify_hypothesis_kernel<<<(H + kHypThreads - 1) / kHypThreads, kHypThreads, 0, s>>>(xy, M, Mdev, Mpad, H, seed,
+                                                                                       models, count);
     // hypotheses per workgroup: 64, halved while the grid has fewer than four workgroups per CU
     const int tiles = Mpad / kVerifyTile;
     // (the chunks go to grid.y: at most 65535, which 64 per workgroup keeps for H <= kVerifyMaxHyps)
     int hc = kScoreHyps;
     while (hc > 1 && (long long)tiles * ((H + hc - 1) / hc) < 4ll * nCU && (H + hc / 2 - 1) / (hc / 2) <= 65535)
         hc >>= 1;
-    verify_score_kernel<<<dim3(tiles, (H + hc - 1) / hc), kScoreThreads, 0, s>>>(xy, Mpad, models, H, hc, tau2, count);
+    verify_score_kernel<<<dim3(tiles, (H + hc - 1) / hc), kScoreThreads, 0, s>>>(xy, Mdev, Mpad, models, H, hc, tau2,
+                                                                                 count);
     verify_argmax_kernel<<<1, 256, 0, s>>>(count, models, H, best, E);
-    if (withMask) verify_mask_kernel<<<(M + 255) / 256, 256, 0, s>>>(xy, M, Mpad, best, E, tau2, flag, mask);
+    if (withMask) verify_mask_kernel<<<(M + 255) / 256, 256, 0, s>>>(xy, M, Mdev, Mpad, best, E, tau2, flag, mask);
 }
 
 }  // namespace fm3d

@@ -692,6 +692,46 @@ int fm3d_pipeline_run_verified(fm3d_ctx *ctx, const fm3d_verify_opts *opts, fm3d
                                fm3d_pipeline_stats *stats, fm3d_verify_report *report);
 int fm3d_pipeline_run_dlt_verified(fm3d_ctx *ctx, const fm3d_verify_opts *opts, int *nInliers,
                                    fm3d_pipeline_stats *stats, fm3d_verify_report *report);
+/* The verified runs as submit / wait, in filter mode (poseFromModel = 0), for a stream of frame pairs
+   ("Submit / wait"): no host round trip between the stages.
+   - fm3d_pipeline_submit_verified stages the pair as fm3d_pipeline_submit does (queryOffset 0) and queues
+     the match stage, the verification, the compaction of the verified matches, the DLT, the LM, the
+     records and the small D2H; fm3d_pipeline_submit_dlt_verified queues the front half (up to the DLT)
+     on the staged inputs, as fm3d_pipeline_submit_dlt does.  Both return without waiting for the
+     device: the match count stays on the device, the verification's launches are sized by the staged
+     nA and read the count there, and what the report needs is stored to page-locked memory in stream
+     order.  The working memory is the context's, sized by nA and reused: a loop allocates nothing
+     after its first pair.
+   - After fm3d_pipeline_wait_verified / fm3d_pipeline_wait_dlt_verified, *nKept / *nInliers, the
+     records (out: host, capacity cap, may be NULL), stats.queries, trains, matches, inliers and kept,
+     report.matches, verified, best, roundsAdopted, E, g12, votes (0) and poseInstalled (0), and what a
+     following fm3d_pipeline_dlt_download returns are, byte for byte, those of
+     fm3d_pipeline_run_verified / fm3d_pipeline_run_dlt_verified for the same inputs, settings, pose
+     and options.  Fm3d.guidedMatchPx and Fm3d.crossCheck act as there.
+   - No model (fewer than 8 matches, or no valid hypothesis): verified = 0, zero records / inliers,
+     FM3D_OK, an all-zero E.  Unlike the synchronous call the DLT and the LM are queued; they see no
+     item, and nothing on the host decides it.
+   - The context's pose is never changed.  report.verify_ms comes from the events around the
+     verification; the stage times follow fm3d_pipeline_wait's and fm3d_pipeline_wait_dlt's rules.
+   - A verified submit is a pending pair: until its own wait every other pipeline call on the context
+     fails with FM3D_ERR_INVALID, fm3d_pipeline_wait / _wait_dlt / _wait_ncc with a message that names
+     the right wait; a verified wait without its submit fails likewise.  A failed submit leaves the
+     context idle.
+   FM3D_ERR_INVALID, before any launch: fm3d_pipeline_run_verified's rules (the submit calls take no
+   report; the wait calls reject a null one); fm3d_pipeline_submit_dlt_verified needs a staged pair.
+   FM3D_ERR_UNSUPPORTED: poseFromModel = 1 (the pose's installation runs on the host's libm: the
+   synchronous calls serve it); a context that is a member or a leader of fm3d_pipeline_link; a staged
+   queryOffset != 0 (submit_dlt_verified); more than 2^20 hypotheses.
+   FM3D_ERR_HIP at the wait: a count outside [0, nA]. */
+int fm3d_pipeline_submit_verified(fm3d_ctx *ctx, const fm3d_verify_opts *opts, const void *descA, int nA,
+                                  const void *descB, int nB, int dim, int type, const fm3d_point2f *kpts1,
+                                  const fm3d_point2f *kpts2, const uint8_t *img1, const uint8_t *img2, int width,
+                                  int height);
+int fm3d_pipeline_wait_verified(fm3d_ctx *ctx, fm3d_record *out, int cap, int *nKept, fm3d_pipeline_stats *stats,
+                                fm3d_verify_report *report);
+int fm3d_pipeline_submit_dlt_verified(fm3d_ctx *ctx, const fm3d_verify_opts *opts);
+int fm3d_pipeline_wait_dlt_verified(fm3d_ctx *ctx, int *nInliers, fm3d_pipeline_stats *stats,
+                                    fm3d_verify_report *report);
 /* BASELINE.json's C3 as worded ("Hamming popcount match + 64x64 patch NCC over 16 normal hypotheses"):
    match -> NNDR -> triangulate, then fm3d_ncc_hypotheses' scoring of every inlier on the device
    (pixelsRay 32 gives the 64 x 64 neighbourhood); *nPoints = inliers scored; stats.lm_ms is the NCC
