@@ -53,6 +53,7 @@ EXPORTS = (
     "fm3d_pipeline_run_verified", "fm3d_pipeline_run_dlt_verified",
     "fm3d_pipeline_submit_verified", "fm3d_pipeline_wait_verified", "fm3d_pipeline_submit_dlt_verified",
     "fm3d_pipeline_wait_dlt_verified",
+    "fm3d_pipeline_describe",
 )
 
 # include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
@@ -165,6 +166,18 @@ class PipelineStats(ctypes.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "lm"}
         d["lm"] = self.lm.as_dict()
         return d
+
+
+class DescribeStats(ctypes.Structure):
+    """fm3d_describe_stats (fm3d_pipeline_describe)."""
+    _fields_ = [("points", ctypes.c_int64), ("patchSize", ctypes.c_int32), ("cols", ctypes.c_int32),
+                ("type", ctypes.c_int32), ("chunks", ctypes.c_int32), ("total_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+DESCRIBE_SOURCES = {"records": 0, "ncc": 1}  # FM3D_DESCRIBE_RECORDS, FM3D_DESCRIBE_NCC
 
 
 class VerifyOpts(ctypes.Structure):
@@ -1285,6 +1298,29 @@ class Pipeline:
         self.ctx.check(lib().fm3d_records_download(self.ctx.handle, ctypes.c_void_p(records_dev_ptr or 0), n,
                                                    _vp(out)))
         return out[:n]
+
+    def describe(self, n: int, source="records", records_dev_ptr: int | None = None, frames: bool = False,
+                 patches: bool = False):
+        """fm3d_pipeline_describe: the tail (main.cpp:157-183) on the device for the n records of the last
+        run (or of the caller's device buffer), or with source="ncc" for the last run_ncc's points and
+        best normals.  Returns (descriptor rows (n, cols), frames (n, 4, 4) | None, patches
+        (n, size, size) | None, stats dict); only patches=True moves a patch to the host."""
+        src = DESCRIBE_SOURCES.get(source, source)
+        if not isinstance(src, int):
+            raise ValueError(f"source must be one of {sorted(DESCRIBE_SOURCES)}")
+        cols, typ = ctypes.c_int(0), ctypes.c_int(0)
+        rc = lib().fm3d_descriptor_info(self.ctx.handle, ctypes.byref(cols), ctypes.byref(typ))
+        dt = np.uint8 if rc == FM3D_OK and typ.value == DESC_BITS else np.float32
+        size = max(lib().fm3d_patch_size(ctypes.byref(self.ctx.settings)), 0)
+        m = max(n, 1)
+        desc = np.zeros((m, max(cols.value, 1)), dtype=dt)
+        fr = np.zeros((m, 4, 4)) if frames else None
+        pa = np.zeros((m, size, size), dtype=np.uint8) if patches else None
+        st = DescribeStats()
+        self.ctx.check(lib().fm3d_pipeline_describe(self.ctx.handle, src, ctypes.c_void_p(records_dev_ptr or 0), n,
+                                                    _vp(desc), _vp(fr), _vp(pa), ctypes.byref(st)))
+        n = max(n, 0)
+        return (desc[:n], fr[:n] if frames else None, pa[:n] if patches else None, st.as_dict())
 
 
 SHARE_BLOCK = 4096  # queries per block of the block-cyclic partition (fm3d_mgpu, shard.py)

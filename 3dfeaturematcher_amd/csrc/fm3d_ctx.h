@@ -123,6 +123,7 @@ enum Ev {
     EV_VERIFY_START, EV_VERIFY_END,  // the verified runs and submits: around the verification
     EV_NORMAL_START, EV_NORMAL_END,  // around the normal stage (LM or NCC scoring)
     EV_SUBMIT_START,  // a submit, before its inputs' H2D
+    EV_TAIL_START,    // fm3d_pipeline_describe: before its first launch
     EV_COUNT
 };
 
@@ -196,6 +197,13 @@ struct fm3d_ctx {
     // on demand, reused across pairs) and the compaction's output, swapped with `matches` once it holds
     // the verified ones
     DevBuf verWork, verMatches;
+    // fm3d_pipeline_describe (fm3d_tail.cpp): per point the frame, R, t and descriptor row; one chunk of
+    // patches; the per-patch constant tables of tailCap patches of edge tailSize (centred keypoint of
+    // angle tailAngle, SiftLevel rows, level indices), the SIFT blur taps of tailSigma and the
+    // oriented path's kept sum
+    DevBuf tailFrames, tailRT, tailDesc, tailPatch, tailKp, tailGL, tailLvl, tailTaps, tailSum;
+    int tailCap = 0, tailSize = 0, tailNTaps = 0;
+    float tailAngle = 0.f, tailSigma = 0.f;
     // pinned staging: descriptors A / B (padded rows), keypoints, images, small tables, results
     HostBuf hA, hB, hK1, hK2, hImg, hTab, hProj, hSmall, hFlag;
     HostBuf hVer;  // a verified submit's fm3d::VerifySmall, stored by launch_verify_report
@@ -290,6 +298,13 @@ struct MatchOpts {
     int crossCheck = 0;
 };
 int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, const MatchOpts& o);
+
+// ---- fm3d_features.cpp: what fm3d_pipeline_describe shares with the one-shot patch descriptors
+int surf_patch_gws(int size);                    // the centred patch keypoint's wavelet size, 2 * round(2 s)
+int ensure_surf_dw(fm3d_ctx* c);                 // c->sfDW: SURF's 20 x 20 Gaussian, uploaded once
+const fm3d::SurfOri& surf_ori_samples();         // SURFInvoker's orientation disc
+// sift_patches' checks and its level-0 blur taps (sigma -> sig_diff)
+int sift_patch_taps(fm3d_ctx* c, std::vector<float>& taps);
 
 // ---- fm3d_lm.cpp
 // One frame pair's points for an LM launch: its context (pyramids c->lvlDesc, pose c->R2/t2,

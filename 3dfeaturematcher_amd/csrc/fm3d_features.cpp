@@ -783,6 +783,33 @@ int surf_upload_image(fm3d_ctx* c, const uint8_t* img, int w, int h) {
 
 }  // namespace
 
+// what fm3d_pipeline_describe (fm3d_tail.cpp) shares with the one-shot patch descriptors below
+namespace fm3d_host {
+
+int surf_patch_gws(int size) { return 2 * cv_round_h(2 * ((float)size * 1.2f / 9.0f)); }
+
+int ensure_surf_dw(fm3d_ctx* c) {
+    if (c->sfDW.bytes) return FM3D_OK;
+    const std::vector<float> dw = surf_dw();
+    HIPCHK(c, c->sfDW.ensure(400 * sizeof(float)));
+    HIPCHK(c, hipMemcpyAsync(c->sfDW.p, dw.data(), 400 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // dw leaves scope
+    return FM3D_OK;
+}
+
+const fm3d::SurfOri& surf_ori_samples() { return surf_ori(); }
+
+int sift_patch_taps(fm3d_ctx* c, std::vector<float>& taps) {
+    if (int r = sift_check_settings(c)) return r;
+    const float sigma = (float)c->s.siftSigma;
+    taps = sift_gauss_kernel(std::sqrt(std::max(sigma * sigma - 0.5f * 0.5f, 0.01f)));
+    if ((int)taps.size() > kSiftMaxTaps)
+        return fail(c, FM3D_ERR_UNSUPPORTED, "SIFT sigma too large for the GPU blur tile (kernel > 65 taps)");
+    return FM3D_OK;
+}
+
+}  // namespace fm3d_host
+
 extern "C" {
 
 int fm3d_surf_detect(fm3d_ctx* c, const uint8_t* img, int w, int h, fm3d_keypoint* kpts, int cap, int* n,

@@ -483,6 +483,16 @@ void launch_square_neighborhoods(const double* frames, int P, int size, double e
 void launch_export_patches(const double* frames, int P, int size, double eps, double inc, const Camera& cam,
                            const uint8_t* img, int w, int h, double* RT, uint8_t* patches, double* imagePoints,
                            hipStream_t s);
+// fm3d_pipeline_describe: launch_features_frames and launch_export_patches' R, t in one pass over
+// points and normals that lie on the device -- the 64-byte records (rec), or with rec null the rows
+// pts / nrm.  frames: 16 doubles per point, RT: 12.
+void launch_tail_frames(const fm3d_record* rec, const double* pts, const double* nrm, int P, const double g[3],
+                        double* frames, double* RT, hipStream_t s);
+// launch_export_patches' patch launch alone, over P <= 65535 rows of RT
+void launch_patches(const double* RT, int P, int size, double eps, double inc, const Camera& cam, const uint8_t* img,
+                    int w, int h, uint8_t* patches, hipStream_t s);
+// *sum += *count (device words; one thread, a vector atomic add)
+void launch_add_count(const int* count, int* sum, hipStream_t s);
 
 // ---------------- records ----------------
 // nDev (may be null): the count on the device, nInl / n its bound

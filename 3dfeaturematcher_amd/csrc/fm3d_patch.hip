@@ -5,11 +5,13 @@
 // SingleCameraTriangulator::projectReferencePointsToImageWithFrame(s)
 // (singlecameratriangulator.cpp:769-849).  main.cpp:157-180 runs them after the normals.
 //
-// Four kernels, all bit-exact against oracle/fm3d_oracle.c (deterministic-math mode):
+// The kernels, all bit-exact against oracle/fm3d_oracle.c (deterministic-math mode):
 //   frames_kernel        one thread per point: z = n, x = g x z, y = z x x, cv::normalize(x), (y),
 //                        columns through Vec::dot, translation = the point;
 //   frame_camera_kernel  one thread per frame: decomposeTransformation + the cvRodrigues2 round trip
 //                        cvProjectPoints2 applies (matrix -> vector -> matrix);
+//   tail_frames_kernel   both of them in one pass over records or point / normal rows on the device
+//                        (fm3d_pipeline_describe); the three share feature_frame and frame_camera;
 //   patch_kernel         one thread per (reference point, frame): projectPoints, isPixelGood(p, 1.0)
 //                        of image 1, (uchar) bilinear sample, written transposed (patch.at(col, row));
 //   square_neighborhoods_kernel  NeighborhoodsGenerator::computeSquareNeighborhoodsByNormals
@@ -41,24 +43,21 @@ __device__ inline void normalize3(double v[3]) {
     for (int i = 0; i < 3; i++) v[i] = v[i] * scale + 0.;
 }
 
-__global__ void frames_kernel(const double* __restrict__ pts, const double* __restrict__ nrm, int P, double g0,
-                              double g1, double g2, double* __restrict__ frames) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    const double z[3] = {nrm[3 * p], nrm[3 * p + 1], nrm[3 * p + 2]};
+// computeFeaturesFrames' frame of one (point, normal z): F, 16 doubles row-major
+__device__ inline void feature_frame(const double z[3], const double pt[3], double g0, double g1, double g2,
+                                     double* F) {
     // x = gravity.cross(z), y = z.cross(x) (cv::Vec3d::cross), normalised afterwards (:476-481)
     double x[3] = {g1 * z[2] - g2 * z[1], g2 * z[0] - g0 * z[2], g0 * z[1] - g1 * z[0]};
     double y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
     normalize3(x);
     normalize3(y);
-    double* F = frames + 16 * (size_t)p;
     for (int r = 0; r < 3; r++) {
         // actualFrame(r, c) = e_r.dot(c-th basis vector) (:484-486)
         const double e[3] = {(double)(r == 0), (double)(r == 1), (double)(r == 2)};
         F[4 * r + 0] = ((0 + e[0] * x[0]) + e[1] * x[1]) + e[2] * x[2];
         F[4 * r + 1] = ((0 + e[0] * y[0]) + e[1] * y[1]) + e[2] * y[2];
         F[4 * r + 2] = ((0 + e[0] * z[0]) + e[1] * z[1]) + e[2] * z[2];
-        F[4 * r + 3] = pts[3 * p + r];
+        F[4 * r + 3] = pt[r];
     }
     F[12] = 0;
     F[13] = 0;
@@ -66,13 +65,19 @@ __global__ void frames_kernel(const double* __restrict__ pts, const double* __re
     F[15] = 1;
 }
 
+__global__ void frames_kernel(const double* __restrict__ pts, const double* __restrict__ nrm, int P, double g0,
+                              double g1, double g2, double* __restrict__ frames) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    const double z[3] = {nrm[3 * p], nrm[3 * p + 1], nrm[3 * p + 2]};
+    const double pt[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+    feature_frame(z, pt, g0, g1, g2, frames + 16 * (size_t)p);
+}
+
 // decomposeTransformation (tools.cpp:101-114) then cvProjectPoints2's Rodrigues: the R, t that
 // projectReferencePointsToImageWithFrame projects with.  cvRodrigues2 (matrix -> vector) first
 // replaces R by its nearest orthonormal matrix, U V^T of OpenCV 2.4's SVD (include/fm3d_cvsvd.h).
-__global__ void frame_camera_kernel(const double* __restrict__ frames, int P, double* __restrict__ RT) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    const double* F = frames + 16 * (size_t)p;
+__device__ inline void frame_camera(const double* F, double* out) {
     const double Rin[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
     double R[9];
     fm3d_cv::polar3(Rin, R);
@@ -105,7 +110,6 @@ __global__ void frame_camera_kernel(const double* __restrict__ frames, int P, do
         rz *= vth;
     }
     // vector -> matrix
-    double* out = RT + 12 * (size_t)p;
     theta = sqrt(rx * rx + ry * ry + rz * rz);
     if (theta < DBL_EPSILON) {
         for (int k = 0; k < 9; k++) out[k] = (k % 4 == 0) ? 1. : 0.;
@@ -124,6 +128,34 @@ __global__ void frame_camera_kernel(const double* __restrict__ frames, int P, do
     out[10] = F[7];
     out[11] = F[11];
 }
+
+__global__ void frame_camera_kernel(const double* __restrict__ frames, int P, double* __restrict__ RT) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    frame_camera(frames + 16 * (size_t)p, RT + 12 * (size_t)p);
+}
+
+// fm3d_pipeline_describe: both of the above in one pass, one thread per point.  The point and the
+// normal come from the 64-byte records (rec) or, rec null, from the rows pts / nrm; the frame is
+// written once and R, t are derived from the same 16 values the frame holds in memory.
+__global__ void tail_frames_kernel(const fm3d_record* __restrict__ rec, const double* __restrict__ pts,
+                                   const double* __restrict__ nrm, int P, double g0, double g1, double g2,
+                                   double* __restrict__ frames, double* __restrict__ RT) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    double z[3], pt[3];
+    for (int k = 0; k < 3; k++) {
+        z[k] = rec ? rec[p].normal[k] : nrm[3 * (size_t)p + k];
+        pt[k] = rec ? rec[p].point[k] : pts[3 * (size_t)p + k];
+    }
+    double F[16];
+    feature_frame(z, pt, g0, g1, g2, F);
+    double* o = frames + 16 * (size_t)p;
+    for (int k = 0; k < 16; k++) o[k] = F[k];
+    frame_camera(F, RT + 12 * (size_t)p);
+}
+
+__global__ void add_count_kernel(const int* __restrict__ count, int* __restrict__ sum) { atomicAdd(sum, *count); }
 
 __global__ __launch_bounds__(256) void patch_kernel(const double* __restrict__ RT, int P, int size, double eps,
                                                     double inc, Camera cam, const uint8_t* __restrict__ img, int w,
@@ -283,6 +315,25 @@ void launch_features_frames(const double* pts, const double* nrm, int P, const d
                             hipStream_t s) {
     if (P <= 0) return;
     hipLaunchKernelGGL(frames_kernel, dim3((P + 255) / 256), dim3(256), 0, s, pts, nrm, P, g[0], g[1], g[2], frames);
+}
+
+void launch_tail_frames(const fm3d_record* rec, const double* pts, const double* nrm, int P, const double g[3],
+                        double* frames, double* RT, hipStream_t s) {
+    if (P <= 0) return;
+    hipLaunchKernelGGL(tail_frames_kernel, dim3((P + 255) / 256), dim3(256), 0, s, rec, pts, nrm, P, g[0], g[1], g[2],
+                       frames, RT);
+}
+
+void launch_patches(const double* RT, int P, int size, double eps, double inc, const Camera& cam, const uint8_t* img,
+                    int w, int h, uint8_t* patches, hipStream_t s) {
+    if (P <= 0 || P > 65535 || size <= 0) return;  // grid.y limit
+    dim3 grid((unsigned)(((size_t)size * size + 255) / 256), (unsigned)P);
+    hipLaunchKernelGGL(patch_kernel, grid, dim3(256), 0, s, RT, P, size, eps, inc, cam, img, w, h, patches,
+                       (double*)nullptr);
+}
+
+void launch_add_count(const int* count, int* sum, hipStream_t s) {
+    hipLaunchKernelGGL(add_count_kernel, dim3(1), dim3(1), 0, s, count, sum);
 }
 
 void launch_export_patches(const double* frames, int P, int size, double eps, double inc, const Camera& cam,

@@ -747,6 +747,47 @@ int fm3d_pipeline_ncc_download(fm3d_ctx *ctx, double *scores, double *normals, i
 /* copy n records from a device record buffer (NULL = internal) to host */
 int fm3d_records_download(fm3d_ctx *ctx, const fm3d_record *recordsDev, int n, fm3d_record *out);
 
+/* ---------------- the tail on the device: records -> frames -> patches -> descriptors ---------------- */
+/* main.cpp:157-183 in one call, for points and normals that already lie in HBM: computeFeaturesFrames,
+   getReferenceSquaredNeighborhood + projectReferencePointsToImageWithFrames on image 1 and
+   extractDescriptorsFromPatches.  The patches are produced and described a chunk at a time in a
+   device buffer of the context; the call waits for the device once, and no patch reaches the host
+   unless `patches` is given.
+   source FM3D_DESCRIBE_RECORDS: n records at recordsDev (device; NULL = the internal record buffer, as
+   fm3d_records_download), after any run or wait that leaves records.  FM3D_DESCRIBE_NCC: the last
+   fm3d_pipeline_run_ncc / wait_ncc -- the points fm3d_pipeline_dlt_download returns and the best
+   normals fm3d_pipeline_ncc_download returns, read where they lie; recordsDev must be NULL and n that
+   run's point count.
+   desc: host, n rows of fm3d_descriptor_info's layout (required when n > 0); frames (may be NULL):
+   host, 16*n doubles; patches (may be NULL): host, n*size*size bytes; stats (may be NULL).
+   All three are byte for byte what fm3d_records_download (or the two NCC downloads) ->
+   fm3d_features_frames -> fm3d_export_patches -> fm3d_extract_descriptors_from_patches give on the
+   same context, NaN frames included, and the chain's failures are this call's, each FM3D_ERR_INVALID
+   with the one-shot's message: a SURF patch keypoint that the wavelet test drops (the same answer for
+   every patch of one size, so it is given before any launch, as the one-shot gives it) or, with
+   Upright 0, one without an orientation sample (the kept keypoints are summed on the device over all
+   chunks and the sum is read once, with the results).
+   Extractors: SURF and SIFT; ORB, BRISK and FREAK are FM3D_ERR_UNSUPPORTED here (their one-shot
+   fm3d_extract_descriptors_from_patches_any stays).
+   FM3D_ERR_INVALID, before any launch: a null context, n < 0, a source outside {0, 1}, a null desc
+   with n > 0, NCC with a recordsDev or with n other than the last NCC run's count (none yet: 0), no
+   image 1 (fm3d_set_images / fm3d_pipeline_upload), a patch size <= 0, a pending submit of any kind.
+   n == 0: FM3D_OK at once, stats zeroed.
+   The chunk is a constant; FM3D_DESCRIBE_CHUNK in the environment, read at every
+   call and clamped to 1 .. 65535, overrides it. */
+#define FM3D_DESCRIBE_RECORDS 0 /* points / normals of fm3d_record rows on the device */
+#define FM3D_DESCRIBE_NCC 1     /* the last fm3d_pipeline_run_ncc / wait_ncc: its inlier points and best normals */
+
+typedef struct fm3d_describe_stats {
+    int64_t points;                /* n */
+    int32_t patchSize, cols, type; /* fm3d_patch_size, fm3d_descriptor_info */
+    int32_t chunks;                /* chunk launches */
+    double total_ms;               /* HIP events around everything queued */
+} fm3d_describe_stats;
+
+int fm3d_pipeline_describe(fm3d_ctx *ctx, int source, const fm3d_record *recordsDev, int n, void *desc, double *frames,
+                           uint8_t *patches, fm3d_describe_stats *stats);
+
 /* ---------------- several GPUs of one node, one process ---------------- */
 /* The reference runs main.cpp:91-155 in one process on one device; these calls are the same
    pipeline over ndev devices.  The queries split into `shares` logical shares (blocks of `block`
