@@ -54,6 +54,7 @@ EXPORTS = (
     "fm3d_pipeline_submit_verified", "fm3d_pipeline_wait_verified", "fm3d_pipeline_submit_dlt_verified",
     "fm3d_pipeline_wait_dlt_verified",
     "fm3d_pipeline_describe",
+    "fm3d_pipeline_describe_any", "fm3d_patch_keypoint_kept", "fm3d_patch_keypoint_kept_for",
 )
 
 # include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
@@ -668,6 +669,13 @@ class Features:
         self.ctx.check(lib().fm3d_compute(self.ctx.handle, _ptr(img, ctypes.c_uint8), w, h, _vp(kin), n, _vp(kout),
                                           _ptr(kept, ctypes.c_int32), ctypes.byref(m), _vp(desc)))
         return kout[:m.value], kept[:m.value], desc[:m.value]
+
+    def patch_keypoint_kept(self, size: int) -> bool:
+        """fm3d_patch_keypoint_kept: whether the settings' extractor keeps the centred keypoint of a
+        size x size patch (extractDescriptorsFromPatches' keypoint); one answer for every patch of a size"""
+        kept = ctypes.c_int(0)
+        self.ctx.check(lib().fm3d_patch_keypoint_kept(self.ctx.handle, int(size), ctypes.byref(kept)))
+        return bool(kept.value)
 
     def set_freak_pairs(self, pairs=None):
         """fm3d_freak_set_pairs: FREAK's 512 selected pairs (indices into the 903 point pairs); None restores
@@ -1305,6 +1313,9 @@ class Pipeline:
         run (or of the caller's device buffer), or with source="ncc" for the last run_ncc's points and
         best normals.  Returns (descriptor rows (n, cols), frames (n, 4, 4) | None, patches
         (n, size, size) | None, stats dict); only patches=True moves a patch to the host."""
+        return self._describe(lib().fm3d_pipeline_describe, n, source, records_dev_ptr, frames, patches)
+
+    def _describe(self, call, n, source, records_dev_ptr, frames, patches):
         src = DESCRIBE_SOURCES.get(source, source)
         if not isinstance(src, int):
             raise ValueError(f"source must be one of {sorted(DESCRIBE_SOURCES)}")
@@ -1317,10 +1328,18 @@ class Pipeline:
         fr = np.zeros((m, 4, 4)) if frames else None
         pa = np.zeros((m, size, size), dtype=np.uint8) if patches else None
         st = DescribeStats()
-        self.ctx.check(lib().fm3d_pipeline_describe(self.ctx.handle, src, ctypes.c_void_p(records_dev_ptr or 0), n,
-                                                    _vp(desc), _vp(fr), _vp(pa), ctypes.byref(st)))
+        self.ctx.check(call(self.ctx.handle, src, ctypes.c_void_p(records_dev_ptr or 0), n, _vp(desc), _vp(fr), _vp(pa),
+                            ctypes.byref(st)))
         n = max(n, 0)
         return (desc[:n], fr[:n] if frames else None, pa[:n] if patches else None, st.as_dict())
+
+    def describe_any(self, n: int, source="records", records_dev_ptr: int | None = None, frames: bool = False,
+                     patches: bool = False):
+        """fm3d_pipeline_describe_any: describe() for every extractor of the settings -- ORB rows (n, 32)
+        uint8 from one launch per chunk, BRISK / FREAK (n, 64) zero rows while their border filter drops
+        the centred keypoint (every patch edge below 634 / 680; from there on ERR_UNSUPPORTED), SURF and
+        SIFT as describe().  The same return shape."""
+        return self._describe(lib().fm3d_pipeline_describe_any, n, source, records_dev_ptr, frames, patches)
 
 
 SHARE_BLOCK = 4096  # queries per block of the block-cyclic partition (fm3d_mgpu, shard.py)

@@ -166,6 +166,12 @@ struct fm3d_ctx {
     // ORB detection / description
     DevBuf orbPyr, orbTab, orbLev, orbMap, orbFlag, orbPos, orbKp, orbR, orbBlur, orbDesc, orbPat;
     std::vector<int> orbUserPattern;  // fm3d_orb_set_pattern (empty: makeRandomPattern(orbPatchSize))
+    // the patch path's offset table (launch_orb_offset_table): 512 (dx, dy), the pattern, patch size and
+    // keypoint angle it was built from, and its largest |offset| + 3 (0: no table; orb_patch_prepare)
+    DevBuf orbOffTab;
+    std::vector<int> orbTabPattern;
+    int orbTabPatchSize = 0, orbTabReach = 0;
+    float orbTabAngle = 0.f;
     // SIFT detection / description
     DevBuf siftImg, siftBase, siftG, siftD, siftGL, siftDL, siftTaps, siftScan, siftFlag, siftPos, siftCand, siftAng,
         siftNpk, siftKp, siftDesc;
@@ -305,6 +311,20 @@ int ensure_surf_dw(fm3d_ctx* c);                 // c->sfDW: SURF's 20 x 20 Gaus
 const fm3d::SurfOri& surf_ori_samples();         // SURFInvoker's orientation disc
 // sift_patches' checks and its level-0 blur taps (sigma -> sig_diff)
 int sift_patch_taps(fm3d_ctx* c, std::vector<float>& taps);
+// ORB on patches of one edge, before any launch: orb_check_settings, the keep rule (FM3D_ERR_INVALID "ORB
+// drops the first patch's keypoint..."), the offset table of the centred keypoint (built on first use
+// and after a change of pattern, orbPatchSize or angle; the only wait) and launch_orb_patch_desc's
+// border guard against the table's own reach
+int orb_patch_prepare(fm3d_ctx* c, int size);
+// m patches on the device -> m x 32 bytes on the device, queued on the context stream
+void orb_patch_describe(fm3d_ctx* c, const uint8_t* patchesDev, int m, int size, uint8_t* rowsDev);
+// the border BRISK's and FREAK's compute demand around a keypoint of this size: brisk::size_of of its
+// scale, freak::pattern().sizes of its scale
+int brisk_border(float kpSize);
+int freak_border(float kpSize);
+
+// ---- fm3d_tail.cpp
+int describe_chunk();  // patches per chunk: the constant, or FM3D_DESCRIBE_CHUNK clamped to 1 .. 65535
 
 // ---- fm3d_lm.cpp
 // One frame pair's points for an LM launch: its context (pyramids c->lvlDesc, pose c->R2/t2,

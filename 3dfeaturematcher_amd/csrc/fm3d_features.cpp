@@ -266,7 +266,7 @@ int orb_retain_best(fm3d_keypoint* k, int n, int npts) {
 }
 
 // the 512-point pattern: the caller's, else makeRandomPattern(patchSize) (cv::RNG(0x34985739))
-int orb_upload_pattern(fm3d_ctx* c, int patchSize) {
+std::vector<int> orb_pattern(const fm3d_ctx* c, int patchSize) {
     std::vector<int> xy = c->orbUserPattern;
     if (xy.empty()) {
         uint64_t state = 0x34985739;
@@ -276,6 +276,11 @@ int orb_upload_pattern(fm3d_ctx* c, int patchSize) {
             xy.push_back((int)((unsigned)state % (unsigned)(b - a) + (unsigned)a));
         }
     }
+    return xy;
+}
+
+int orb_upload_pattern(fm3d_ctx* c, int patchSize) {
+    const std::vector<int> xy = orb_pattern(c, patchSize);
     HIPCHK(c, c->orbPat.ensure(1024 * sizeof(int)));
     HIPCHK(c, hipMemcpyAsync(c->orbPat.p, xy.data(), 1024 * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -808,6 +813,46 @@ int sift_patch_taps(fm3d_ctx* c, std::vector<float>& taps) {
     return FM3D_OK;
 }
 
+int orb_patch_prepare(fm3d_ctx* c, int size) {
+    int r, kept = 0;
+    if ((r = orb_check_settings(c))) return r;
+    if ((r = fm3d_patch_keypoint_kept(c, size, &kept))) return fail(c, r, "patch keypoint: no keep rule");
+    if (!kept)
+        return fail(c, FM3D_ERR_INVALID, "ORB drops the first patch's keypoint (the reference's rows would have 0 columns)");
+    // descriptorsmatcher.cpp:146-158: every patch's keypoint has angle -1, so one table serves them all
+    const float angle = -1.f;
+    const int patchSize = c->s.orbPatchSize;
+    std::vector<int> xy = orb_pattern(c, patchSize);
+    if (!c->orbTabReach || patchSize != c->orbTabPatchSize || angle != c->orbTabAngle || xy != c->orbTabPattern) {
+        c->orbTabReach = 0;
+        hipSetDevice(c->device);
+        int2 tab[512];
+        HIPCHK(c, c->orbPat.ensure(1024 * sizeof(int)));
+        HIPCHK(c, c->orbOffTab.ensure(sizeof(tab)));
+        HIPCHK(c, hipMemcpyAsync(c->orbPat.p, xy.data(), 1024 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        fm3d::launch_orb_offset_table(c->orbPat.as<int>(), angle, c->orbOffTab.as<int2>(), c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(tab, c->orbOffTab.p, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // xy is read, tab is written
+        long reach = 0;
+        for (const int2& o : tab) reach = std::max({reach, std::labs((long)o.x), std::labs((long)o.y)});
+        if (reach > (1 << 20)) return fail(c, FM3D_ERR_INVALID, "ORB pattern offsets out of range");
+        c->orbTabPattern.swap(xy);
+        c->orbTabPatchSize = patchSize;
+        c->orbTabAngle = angle;
+        c->orbTabReach = (int)reach + 3;  // the 7 x 7 blur around the farthest test point
+    }
+    // launch_orb_patch_desc has no border branch: every read of the blur lies inside the patch
+    const int ctr = size / 2;
+    if (ctr - c->orbTabReach < 0 || ctr + c->orbTabReach >= size)
+        return fail(c, FM3D_ERR_INVALID, "ORB pattern reaches past the patch border");
+    return FM3D_OK;
+}
+
+void orb_patch_describe(fm3d_ctx* c, const uint8_t* patchesDev, int m, int size, uint8_t* rowsDev) {
+    fm3d::launch_orb_patch_desc(patchesDev, m, size, c->orbOffTab.as<int2>(), orb_blur_kernel(), rowsDev, c->stream);
+}
+
 }  // namespace fm3d_host
 
 extern "C" {
@@ -961,18 +1006,36 @@ int fm3d_extract_descriptors_from_patches_any(fm3d_ctx* c, const uint8_t* patche
     const int cols = ex == FM3D_FEAT_ORB ? 32 : 64;
     uint8_t* d = static_cast<uint8_t*>(desc);
     std::memset(d, 0, (size_t)P * cols);
+    if (ex == FM3D_FEAT_ORB) {
+        // every patch has the same keypoint, so the keep rule and the rotated pattern are settled once;
+        // then the tail's kernel on chunks of the tail's size, uploaded one after the other
+        if (P == 0) return FM3D_OK;
+        int r;
+        if ((r = orb_patch_prepare(c, size))) return r;
+        hipSetDevice(c->device);
+        const int chunk = std::min(describe_chunk(), P);
+        const size_t per = (size_t)size * size;
+        HIPCHK(c, c->tailPatch.ensure((size_t)chunk * per));
+        HIPCHK(c, c->tailDesc.ensure((size_t)P * cols));
+        for (int p0 = 0; p0 < P; p0 += chunk) {
+            const int m = std::min(chunk, P - p0);
+            HIPCHK(c, hipMemcpyAsync(c->tailPatch.p, patches + per * p0, per * m, hipMemcpyHostToDevice, c->stream));
+            orb_patch_describe(c, c->tailPatch.as<uint8_t>(), m, size, c->tailDesc.as<uint8_t>() + (size_t)p0 * cols);
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipMemcpyAsync(d, c->tailDesc.p, (size_t)P * cols, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return FM3D_OK;
+    }
     const float center = (float)(int)std::floor(size / 2);
     const fm3d_keypoint k{center, center, (float)size, -1.f, 1.f, 0, 0};
     for (int p = 0; p < P; p++) {
         fm3d_keypoint ko;
         int m = 0, r;
         const uint8_t* img = patches + (size_t)p * size * size;
-        r = ex == FM3D_FEAT_ORB     ? fm3d_orb_compute(c, img, size, size, &k, 1, &ko, nullptr, &m, d + (size_t)p * cols)
-            : ex == FM3D_FEAT_BRISK ? fm3d_brisk_compute(c, img, size, size, &k, 1, &ko, nullptr, &m, d + (size_t)p * cols)
-                                    : fm3d_freak_compute(c, img, size, size, &k, 1, &ko, nullptr, &m, d + (size_t)p * cols);
+        r = ex == FM3D_FEAT_BRISK ? fm3d_brisk_compute(c, img, size, size, &k, 1, &ko, nullptr, &m, d + (size_t)p * cols)
+                                  : fm3d_freak_compute(c, img, size, size, &k, 1, &ko, nullptr, &m, d + (size_t)p * cols);
         if (r) return r;
-        if (p == 0 && m == 0 && ex == FM3D_FEAT_ORB)
-            return fail(c, FM3D_ERR_INVALID, "ORB drops the first patch's keypoint (the reference's rows would have 0 columns)");
     }
     return FM3D_OK;
 }
@@ -1045,6 +1108,7 @@ int fm3d_orb_set_pattern(fm3d_ctx* c, const int32_t* xy, int npoints) {
     if (!c || (xy && npoints != 512)) return FM3D_ERR_INVALID;
     c->orbUserPattern.clear();
     if (xy) c->orbUserPattern.assign(xy, xy + 1024);
+    c->orbTabReach = 0;  // the patch path's offset table is of the old pattern
     return FM3D_OK;
 }
 
@@ -1732,6 +1796,12 @@ int mser_detect(fm3d_ctx* c, const uint8_t* img, int count, int w, int h, const 
 }
 }  // namespace
 
+// for fm3d_patch_keypoint_kept: the border that brisk_compute / freak_compute hold a keypoint's size to
+namespace fm3d_host {
+int brisk_border(float kpSize) { return brisk::size_of(brisk::kscale(kpSize)); }
+int freak_border(float kpSize) { return freak::pattern().sizes[freak::kscale(kpSize)]; }
+}  // namespace fm3d_host
+
 extern "C" {
 int fm3d_mser_detect(fm3d_ctx* c, const uint8_t* img, int w, int h, int delta, int minArea, int maxArea,
                      double maxVariation, double minDiversity, fm3d_keypoint* kpts, int cap, int* n) {
@@ -2075,6 +2145,42 @@ int fm3d_orb_compute(fm3d_ctx* c, const uint8_t* img, int w, int h, const fm3d_k
     }
     *nOut = m;
     return FM3D_OK;
+}
+
+int fm3d_patch_keypoint_kept_for(const fm3d_settings* s, int size, int* kept) {
+    if (!s || !kept || size <= 0) return FM3D_ERR_INVALID;
+    // descriptorsmatcher.cpp:146-158: the keypoint of every patch of this edge, on a size x size image
+    const float ctr = (float)(int)std::floor(size / 2), ks = (float)size;
+    switch (s->extractorType) {
+    case FM3D_FEAT_SURF:  // fm3d_surf_compute: the wavelet against the image
+        *kept = size + 1 >= surf_patch_gws(size);
+        return FM3D_OK;
+    case FM3D_FEAT_SIFT:
+        *kept = 1;
+        return FM3D_OK;
+    case FM3D_FEAT_ORB: {  // fm3d_orb_compute: runByImageBorder(edgeThreshold) on the rounded position
+        const int b = s->orbEdgeThreshold;
+        const long i = std::lrint(ctr);
+        *kept = b <= 0 || (size > 2 * b && i >= b && i < b + (size - 2 * b));
+        return FM3D_OK;
+    }
+    case FM3D_FEAT_BRISK: {  // brisk_compute: the scale's pattern size as the border
+        const int b = brisk_border(ks);
+        *kept = !(ctr < (float)b || ctr >= (float)(size - b));
+        return FM3D_OK;
+    }
+    case FM3D_FEAT_FREAK: {  // freak_compute
+        const float ps = (float)freak_border(ks);
+        *kept = !(ctr <= ps || ctr >= size - ps);
+        return FM3D_OK;
+    }
+    default:
+        return FM3D_ERR_UNSUPPORTED;
+    }
+}
+
+int fm3d_patch_keypoint_kept(const fm3d_ctx* c, int size, int* kept) {
+    return c ? fm3d_patch_keypoint_kept_for(&c->s, size, kept) : FM3D_ERR_INVALID;
 }
 
 }  // extern "C"

@@ -274,6 +274,14 @@ void launch_orb_blur(const uint8_t* pyr, const OrbLevel* L, int nL, long long to
                      uint8_t* out, hipStream_t s);
 void launch_orb_desc(const uint8_t* blur, const OrbLevel* L, const fm3d_keypoint* kp, int n, const int* pattern,
                      uint8_t* desc, hipStream_t s);
+// tab[0..512): launch_orb_desc's rotated, rounded (dx, dy) of the 512 pattern points at a keypoint angle
+void launch_orb_offset_table(const int* pattern, float angle, int2* tab, hipStream_t s);
+// m patches of size x size bytes back to back, each with the keypoint (size/2, size/2) of tab's angle on
+// level 0: the rows launch_orb_blur + launch_orb_desc give on each patch, m x 32 bytes (desc 8-byte
+// aligned).  The blur is computed at the test points only and has no border form: the caller checks
+// size/2 - reach >= 0 and size/2 + reach < size for reach = tab's largest |offset| + 3.
+void launch_orb_patch_desc(const uint8_t* patches, int m, int size, const int2* tab, const OrbBlurK& bk, uint8_t* desc,
+                           hipStream_t s);
 
 // ---------------- SIFT (fm3d_sift.hip) ----------------
 struct SiftLevel {    // one pyramid level, levels concatenated float after float

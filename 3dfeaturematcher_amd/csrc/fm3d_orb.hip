@@ -21,7 +21,11 @@
 //                       the columns as SSE2's SymmColumnVec_32s8u (float) on the first floor(w/4)*4
 //                       columns and fixed point on the rest;
 //   orb_desc_kernel     computeOrbDescriptor (WTA_K 2): a thread per descriptor byte, 8 comparisons of
-//                       the rotated pattern points.
+//                       the rotated pattern points;
+//   orb_patch_desc      the same rows for square patches with one centred keypoint each (the tail,
+//                       DESIGN.md §3.5b): orb_offset_table_kernel turns the pattern once for all
+//                       patches, orb_patch_desc_kernel blurs only the pixels the tests read, a block per
+//                       patch and a thread per test, and packs the bits with the wave's ballot.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stdint.h>
@@ -273,6 +277,19 @@ __global__ __launch_bounds__(256) void orb_blur_cols_kernel(const int* __restric
     out[lv.first + (size_t)y * w + x] = (uint8_t)clampi(v, 0, 255);
 }
 
+// computeOrbDescriptor's GET_VALUE addressing: the N pattern points xy[0..2N) turned by the keypoint
+// angle (degrees) and rounded, as (dx, dy) from the keypoint's pixel
+template <int N>
+__device__ __forceinline__ void orb_rotated_offsets(const int* __restrict__ xy, float angle, int2 (&o)[N]) {
+    angle *= (float)(M_PI / 180.f);
+    const float a = (float)fm3d_cos((double)angle), b = (float)fm3d_sin((double)angle);
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const float x = xy[2 * j] * a - xy[2 * j + 1] * b, y = xy[2 * j] * b + xy[2 * j + 1] * a;
+        o[j] = make_int2(cv_roundf(x), cv_roundf(y));
+    }
+}
+
 // a thread per descriptor byte: bit j = I(rot p[16i+2j]) < I(rot p[16i+2j+1]) on the blurred level
 __global__ __launch_bounds__(256) void orb_desc_kernel(const uint8_t* __restrict__ blur, const OrbLevel* __restrict__ L,
                                                        const fm3d_keypoint* __restrict__ kp, int n,
@@ -282,21 +299,58 @@ __global__ __launch_bounds__(256) void orb_desc_kernel(const uint8_t* __restrict
     const int q = (int)(t >> 5), i = (int)(t & 31);
     const fm3d_keypoint k = kp[q];
     const OrbLevel lv = L[k.octave];
-    float angle = k.angle;
-    angle *= (float)(M_PI / 180.f);
-    const float a = (float)fm3d_cos((double)angle), b = (float)fm3d_sin((double)angle);
+    int2 o[16];
+    orb_rotated_offsets(pattern + i * 32, k.angle, o);
     const int w = lv.w;
     const uint8_t* c = blur + lv.first + (size_t)cv_roundf(k.y) * w + cv_roundf(k.x);
     int val = 0;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-        const int* p0 = pattern + (i * 16 + 2 * j) * 2;
-        const float x0 = p0[0] * a - p0[1] * b, y0 = p0[0] * b + p0[1] * a;
-        const float x1 = p0[2] * a - p0[3] * b, y1 = p0[2] * b + p0[3] * a;
-        const int t0 = c[cv_roundf(y0) * w + cv_roundf(x0)], t1 = c[cv_roundf(y1) * w + cv_roundf(x1)];
+        const int t0 = c[o[2 * j].y * w + o[2 * j].x], t1 = c[o[2 * j + 1].y * w + o[2 * j + 1].x];
         val |= (t0 < t1) << j;
     }
     desc[t] = (uint8_t)val;
+}
+
+// ---------------------------------------------------------------- patches: one centred keypoint each
+// The 512 offsets of a keypoint angle, once for every patch: thread t takes pattern point t.
+__global__ __launch_bounds__(512) void orb_offset_table_kernel(const int* __restrict__ pattern, float angle,
+                                                               int2* __restrict__ tab) {
+    int2 o[1];
+    orb_rotated_offsets(pattern + 2 * threadIdx.x, angle, o);
+    tab[threadIdx.x] = o[0];
+}
+
+// GaussianBlur(7x7, 2) at one pixel whose 7 x 7 neighbourhood lies inside the image: orb_blur_rows_kernel's
+// integer row sums and the float column form of orb_blur_cols_kernel, operation for operation
+__device__ __forceinline__ int orb_blur_at(const uint8_t* __restrict__ p, int w, const OrbBlurK& bk) {
+    int R[7];
+#pragma unroll
+    for (int r = 0; r < 7; r++) {
+        const uint8_t* row = p + (r - 3) * w - 3;
+        int s = 0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) s += bk.ik[k] * row[k];
+        R[r] = s;
+    }
+    float s = (float)R[3] * bk.fk[0] + 0.f;
+#pragma unroll
+    for (int k = 1; k <= 3; k++) s = s + (float)(R[3 + k] + R[3 - k]) * bk.fk[k];
+    return clampi((int)rintf(s), 0, 255);
+}
+
+// A block per patch, a thread per test: thread t blurs the two points of test t at their pixels only and
+// its wave's ballot is 8 descriptor bytes (lane l = bit l & 7 of byte l >> 3 of the wave's 8).  No
+// border branch: the launcher's caller has checked that every read lies inside the patch.
+__global__ __launch_bounds__(256) void orb_patch_desc_kernel(const uint8_t* __restrict__ patches, int size,
+                                                             const int2* __restrict__ tab, OrbBlurK bk,
+                                                             unsigned long long* __restrict__ desc) {
+    const int t = threadIdx.x;
+    const uint8_t* c = patches + (size_t)blockIdx.x * size * size + (size_t)(size / 2) * size + size / 2;
+    const int2 o0 = tab[2 * t], o1 = tab[2 * t + 1];
+    const int t0 = orb_blur_at(c + o0.y * size + o0.x, size, bk), t1 = orb_blur_at(c + o1.y * size + o1.x, size, bk);
+    const unsigned long long bits = __ballot(t0 < t1);
+    if ((t & 63) == 0) desc[(size_t)blockIdx.x * 4 + (t >> 6)] = bits;
 }
 
 inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
@@ -345,6 +399,16 @@ void launch_orb_desc(const uint8_t* blur, const OrbLevel* L, const fm3d_keypoint
                      uint8_t* desc, hipStream_t s) {
     if (n <= 0) return;
     orb_desc_kernel<<<blocks((long long)n * 32), 256, 0, s>>>(blur, L, kp, n, pattern, desc);
+}
+
+void launch_orb_offset_table(const int* pattern, float angle, int2* tab, hipStream_t s) {
+    orb_offset_table_kernel<<<1, 512, 0, s>>>(pattern, angle, tab);
+}
+
+void launch_orb_patch_desc(const uint8_t* patches, int m, int size, const int2* tab, const OrbBlurK& bk, uint8_t* desc,
+                           hipStream_t s) {
+    if (m <= 0) return;
+    orb_patch_desc_kernel<<<m, 256, 0, s>>>(patches, size, tab, bk, reinterpret_cast<unsigned long long*>(desc));
 }
 
 }  // namespace fm3d

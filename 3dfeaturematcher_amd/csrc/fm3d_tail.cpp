@@ -1,13 +1,16 @@
-// fm3d_tail.cpp -- fm3d_pipeline_describe: the reference's tail (main.cpp:157-183) for points and
+// fm3d_tail.cpp -- fm3d_pipeline_describe(_any): the reference's tail (main.cpp:157-183) for points and
 // normals that already lie in HBM.  Frames and the patch camera in one launch over all n points, then
 // chunk after chunk the patches into a context buffer and their descriptors read from it in place;
 // the descriptor rows (and the frames) leave in one copy at the end and the host waits once.  The
 // kernels are the one-shot calls' own (fm3d_features_frames, fm3d_export_patches,
-// fm3d_extract_descriptors_from_patches), so the bytes are theirs: DESIGN.md §3.5b.
+// fm3d_extract_descriptors_from_patches), so the bytes are theirs: DESIGN.md §3.5b.  The _any form adds
+// the binary extractors: ORB's rows from launch_orb_patch_desc on each chunk, and the zero rows the
+// reference keeps for a BRISK or FREAK keypoint that its border filter drops.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "fm3d_ctx.h"
@@ -20,12 +23,16 @@ namespace {
 constexpr int kDescribeChunk = 4096;
 constexpr int kChunkMax = 65535;
 
-int describe_chunk() {
+}  // namespace
+
+int fm3d_host::describe_chunk() {
     const char* e = getenv("FM3D_DESCRIBE_CHUNK");
     if (!e || !*e) return kDescribeChunk;
     const long v = strtol(e, nullptr, 10);
     return (int)std::min<long>(std::max<long>(v, 1), kChunkMax);
 }
+
+namespace {
 
 // The per-patch constants of a chunk are the same for every chunk: the centred keypoint
 // (descriptorsmatcher.cpp:146-158), and for SIFT the patch's level row and index.  Built once per
@@ -72,10 +79,9 @@ int ensure_taps(fm3d_ctx* c) {
     return FM3D_OK;
 }
 
-}  // namespace
-
-extern "C" int fm3d_pipeline_describe(fm3d_ctx* c, int source, const fm3d_record* recordsDev, int n, void* desc,
-                                      double* frames, uint8_t* patches, fm3d_describe_stats* stats) {
+// both entry points: `any` admits the binary extractors
+int describe(fm3d_ctx* c, bool any, int source, const fm3d_record* recordsDev, int n, void* desc, double* frames,
+             uint8_t* patches, fm3d_describe_stats* stats) {
     if (!c) return FM3D_ERR_INVALID;
     if (n < 0 || (n && !desc)) return fail(c, FM3D_ERR_INVALID, "null argument or n < 0");
     if (source != FM3D_DESCRIBE_RECORDS && source != FM3D_DESCRIBE_NCC)
@@ -94,9 +100,14 @@ extern "C" int fm3d_pipeline_describe(fm3d_ctx* c, int source, const fm3d_record
     const int size = fm3d_patch_size(&c->s);
     if (size <= 0) return fail(c, FM3D_ERR_INVALID, "patch size <= 0 (Neighborhoods.epsilon / cmPerPixel)");
     const fm3d_settings& S = c->s;
-    const bool sift = S.extractorType == FM3D_FEAT_SIFT;
-    if (!sift && S.extractorType != FM3D_FEAT_SURF)
-        return fail(c, FM3D_ERR_UNSUPPORTED, "only the SURF and SIFT extractors describe patches on the GPU");
+    const int ex = S.extractorType;
+    const bool sift = ex == FM3D_FEAT_SIFT, surf = ex == FM3D_FEAT_SURF;
+    const bool orb = any && ex == FM3D_FEAT_ORB;
+    const bool zeros = any && (ex == FM3D_FEAT_BRISK || ex == FM3D_FEAT_FREAK);  // if it runs at all: see below
+    if (!sift && !surf && !orb && !zeros)
+        return fail(c, FM3D_ERR_UNSUPPORTED,
+                    any ? "the settings' extractor type has no GPU implementation"
+                        : "only the SURF and SIFT extractors describe patches on the GPU");
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n == 0) return FM3D_OK;
 
@@ -105,26 +116,39 @@ extern "C" int fm3d_pipeline_describe(fm3d_ctx* c, int source, const fm3d_record
     double g[3];
     if ((r = fm3d_gravity(&S, g))) return fail(c, r, "gravity: singular rodriguesIC rotation");
     // the centred keypoint's wavelet against the patch (SURFInvoker's drop): one answer for every patch
-    if (!sift && size + 1 < surf_patch_gws(size))
+    if (surf && size + 1 < surf_patch_gws(size))
         return fail(c, FM3D_ERR_INVALID, "patch keypoint dropped by SURF (descriptor row missing)");
+    if (zeros) {
+        // BRISK's and FREAK's border filters keep the centred keypoint from an edge of 634 and 680 only;
+        // below, every row is the reference's Mat::zeros row and no patch is needed for it
+        int kept = 0;
+        if ((r = fm3d_patch_keypoint_kept(c, size, &kept))) return fail(c, r, "patch keypoint: no keep rule");
+        if (kept)
+            return fail(c, FM3D_ERR_UNSUPPORTED,
+                        "BRISK / FREAK keep the centred keypoint of a " + std::to_string(size) +
+                            " px patch: no batched form, use fm3d_extract_descriptors_from_patches_any");
+    }
     hipSetDevice(c->device);
-    const bool oriented = !sift && !S.surfUpright;
+    // ORB: the settings, the keep rule ("ORB drops the first patch's keypoint..."), the offset table of
+    // the centred keypoint and the border guard of launch_orb_patch_desc
+    if (orb && (r = orb_patch_prepare(c, size))) return r;
+    const bool oriented = surf && !S.surfUpright;
     const int chunk = std::min(describe_chunk(), n);
     const size_t per = (size_t)size * size;
-    const size_t rowBytes = (size_t)cols * sizeof(float);
+    const size_t rowBytes = (size_t)cols * (type == FM3D_DESC_BITS ? 1 : sizeof(float));
 
     // first-use tables (each may wait for its upload), then every buffer: n x (frame, R t, row), the
     // rest by the chunk
     if (sift) {
         if ((r = ensure_taps(c))) return r;
-    } else if ((r = ensure_surf_dw(c))) {
+    } else if (surf && (r = ensure_surf_dw(c))) {
         return r;
     }
-    if ((r = ensure_tables(c, chunk, size, sift || oriented ? -1.f : 360.f - 90.f))) return r;
+    if ((sift || surf) && (r = ensure_tables(c, chunk, size, sift || oriented ? -1.f : 360.f - 90.f))) return r;
     HIPCHK(c, c->tailFrames.ensure((size_t)n * 16 * sizeof(double)));
     HIPCHK(c, c->tailRT.ensure((size_t)n * 12 * sizeof(double)));
-    HIPCHK(c, c->tailDesc.ensure((size_t)n * rowBytes));
-    HIPCHK(c, c->tailPatch.ensure((size_t)chunk * per));
+    if (!zeros) HIPCHK(c, c->tailDesc.ensure((size_t)n * rowBytes));
+    if (!zeros || patches) HIPCHK(c, c->tailPatch.ensure((size_t)chunk * per));
     const size_t sumPer = (size_t)(size + 1) * (size + 1);
     if (sift) {
         HIPCHK(c, c->siftBase.ensure((size_t)chunk * per * sizeof(float)));
@@ -154,12 +178,16 @@ extern "C" int fm3d_pipeline_describe(fm3d_ctx* c, int source, const fm3d_record
     const fm3d_keypoint* tkp = c->tailKp.as<fm3d_keypoint>();
     uint8_t* pbuf = c->tailPatch.as<uint8_t>();
     int chunks = 0;
-    for (int p0 = 0; p0 < n; p0 += chunk, chunks++) {
+    for (int p0 = 0; p0 < n && (!zeros || patches); p0 += chunk, chunks++) {
         const int m = std::min(chunk, n - p0);
         fm3d::launch_patches(c->tailRT.as<double>() + 12 * (size_t)p0, m, size, S.neighEpsilon, S.cmPerPixel * 0.01,
                              c->cam, c->pyr1[0].as<uint8_t>(), c->lw[0], c->lh[0], pbuf, c->stream);
         float* rows = reinterpret_cast<float*>(c->tailDesc.as<char>() + (size_t)p0 * rowBytes);
-        if (sift) {
+        if (zeros) {
+            // the patches are the caller's only
+        } else if (orb) {
+            orb_patch_describe(c, pbuf, m, size, reinterpret_cast<uint8_t*>(rows));
+        } else if (sift) {
             fm3d::SiftResize rp{};
             rp.sw = rp.dw = size;
             rp.sh = rp.dh = size;
@@ -192,7 +220,10 @@ extern "C" int fm3d_pipeline_describe(fm3d_ctx* c, int source, const fm3d_record
     if (frames)
         HIPCHK(c, hipMemcpyAsync(frames, c->tailFrames.p, (size_t)n * 16 * sizeof(double), hipMemcpyDeviceToHost,
                                  c->stream));
-    HIPCHK(c, hipMemcpyAsync(desc, c->tailDesc.p, (size_t)n * rowBytes, hipMemcpyDeviceToHost, c->stream));
+    if (zeros)
+        std::memset(desc, 0, (size_t)n * rowBytes);
+    else
+        HIPCHK(c, hipMemcpyAsync(desc, c->tailDesc.p, (size_t)n * rowBytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(c->ev[EV_END], c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev[EV_END]));  // the call's one wait
     if (kept != n) return fail(c, FM3D_ERR_INVALID, "patch keypoint dropped by SURF (no orientation sample)");
@@ -207,4 +238,16 @@ extern "C" int fm3d_pipeline_describe(fm3d_ctx* c, int source, const fm3d_record
         stats->total_ms = ms;
     }
     return FM3D_OK;
+}
+
+}  // namespace
+
+extern "C" int fm3d_pipeline_describe(fm3d_ctx* c, int source, const fm3d_record* recordsDev, int n, void* desc,
+                                      double* frames, uint8_t* patches, fm3d_describe_stats* stats) {
+    return describe(c, false, source, recordsDev, n, desc, frames, patches, stats);
+}
+
+extern "C" int fm3d_pipeline_describe_any(fm3d_ctx* c, int source, const fm3d_record* recordsDev, int n, void* desc,
+                                          double* frames, uint8_t* patches, fm3d_describe_stats* stats) {
+    return describe(c, true, source, recordsDev, n, desc, frames, patches, stats);
 }

@@ -453,12 +453,25 @@ int fm3d_surf_compute(fm3d_ctx *ctx, const uint8_t *img, int width, int height, 
    row per patch. */
 int fm3d_extract_descriptors_from_patches(fm3d_ctx *ctx, const uint8_t *patches, int P, int size, float *desc);
 /* The same for any extractor of the settings, rows laid out as fm3d_descriptor_info says: SURF / SIFT
-   as above (floats), ORB (32 bytes) and BRISK (64 bytes) per patch through their compute on the patch
-   (fm3d_orb_compute / fm3d_brisk_compute).  A patch whose keypoint the extractor drops keeps a zero
-   row, as the reference's Mat::zeros + copyTo of an empty row leaves it (BRISK drops every centred
-   patch keypoint: its pattern reaches ~1.5 x size); FM3D_ERR_INVALID when the first patch's row is
-   dropped by ORB (the reference's matrix would have 0 columns). */
+   as above (floats), BRISK and FREAK (64 bytes) per patch through their compute on the patch
+   (fm3d_brisk_compute / fm3d_freak_compute), ORB (32 bytes) for all patches of a chunk in one launch
+   (the chunk of fm3d_pipeline_describe, uploaded one after the other): the bytes of fm3d_orb_compute
+   on each patch.  A patch whose keypoint the extractor drops keeps a zero row, as the reference's
+   Mat::zeros + copyTo of an empty row leaves it (BRISK drops every centred patch keypoint below an
+   edge of 634, FREAK below 680: their patterns reach ~1.5 x size); FM3D_ERR_INVALID when ORB drops
+   the patches' keypoint (fm3d_patch_keypoint_kept: the reference's matrix would have 0 columns) or
+   when a pattern of fm3d_orb_set_pattern reaches past the patch border. */
 int fm3d_extract_descriptors_from_patches_any(fm3d_ctx *ctx, const uint8_t *patches, int P, int size, void *desc);
+/* Whether the settings' extractor keeps the keypoint extractDescriptorsFromPatches gives every patch of
+   edge `size` -- (floor(size/2), floor(size/2)), size `size`, on a size x size image: SURF's wavelet
+   test (size + 1 >= 2*round(2 * 1.2 size / 9)), ORB's border (size > 2 orbEdgeThreshold and the centre
+   inside it), BRISK's and FREAK's pattern size at the keypoint's scale as the border (kept from 634 and
+   680); SIFT keeps every keypoint.  One answer for every patch of a size, *kept = 1 | 0; host arithmetic
+   only, the filters of fm3d_surf_compute / fm3d_orb_compute / fm3d_brisk_compute / fm3d_freak_compute.
+   The _for form reads the settings alone and needs no context (nor a device).  FM3D_ERR_INVALID: a null
+   argument or size <= 0; FM3D_ERR_UNSUPPORTED: another extractor type. */
+int fm3d_patch_keypoint_kept(const fm3d_ctx *ctx, int size, int *kept);
+int fm3d_patch_keypoint_kept_for(const fm3d_settings *s, int size, int *kept);
 
 /* ---------------- feature detection + description (ORB, OpenCV 2.4) ---------------- */
 /* FeatureDetector::detect of the settings' ORB detector (descriptorsmatcher.cpp:273-279:
@@ -767,8 +780,8 @@ int fm3d_records_download(fm3d_ctx *ctx, const fm3d_record *recordsDev, int n, f
    every patch of one size, so it is given before any launch, as the one-shot gives it) or, with
    Upright 0, one without an orientation sample (the kept keypoints are summed on the device over all
    chunks and the sum is read once, with the results).
-   Extractors: SURF and SIFT; ORB, BRISK and FREAK are FM3D_ERR_UNSUPPORTED here (their one-shot
-   fm3d_extract_descriptors_from_patches_any stays).
+   Extractors: SURF and SIFT; ORB, BRISK and FREAK are FM3D_ERR_UNSUPPORTED here
+   (fm3d_pipeline_describe_any below takes them).
    FM3D_ERR_INVALID, before any launch: a null context, n < 0, a source outside {0, 1}, a null desc
    with n > 0, NCC with a recordsDev or with n other than the last NCC run's count (none yet: 0), no
    image 1 (fm3d_set_images / fm3d_pipeline_upload), a patch size <= 0, a pending submit of any kind.
@@ -787,6 +800,24 @@ typedef struct fm3d_describe_stats {
 
 int fm3d_pipeline_describe(fm3d_ctx *ctx, int source, const fm3d_record *recordsDev, int n, void *desc, double *frames,
                            uint8_t *patches, fm3d_describe_stats *stats);
+/* The same call for every extractor of the settings (as fm3d_extract_descriptors_from_patches_any is to
+   fm3d_extract_descriptors_from_patches): sources, arguments, refusals, chunking, the one wait and the
+   stats are fm3d_pipeline_describe's, and with SURF or SIFT so are the bytes.  stats.type is
+   FM3D_DESC_BITS for the binary extractors, stats.cols 32 (ORB) or 64 (BRISK, FREAK).
+   ORB: per chunk the patches and, read from them in place, their 32-byte rows -- the 256 tests on the
+   7 x 7 Gaussian computed at the test points only, the bytes of fm3d_orb_compute on each patch with
+   its centred keypoint (angle -1, octave 0).  The chunk holds the patches and nothing else.
+   orbNumLevels .. orbFastThreshold are checked as by fm3d_orb_compute (its code and message);
+   FM3D_ERR_INVALID, before any launch, when fm3d_patch_keypoint_kept says the keypoint is dropped
+   ("ORB drops the first patch's keypoint...", as the one-shot call) or when a pattern of
+   fm3d_orb_set_pattern reaches past the patch border.
+   BRISK, FREAK: while fm3d_patch_keypoint_kept says "dropped" (every edge below 634 / 680) the rows
+   are n x 64 zero bytes, the reference's Mat::zeros rows; frames are computed when asked for, and the
+   patches only when asked for (stats.chunks counts their launches, 0 without).  From the edge at which
+   the keypoint is kept: FM3D_ERR_UNSUPPORTED before any launch -- there is no batched form for patches
+   that large; fm3d_extract_descriptors_from_patches_any describes them one by one. */
+int fm3d_pipeline_describe_any(fm3d_ctx *ctx, int source, const fm3d_record *recordsDev, int n, void *desc,
+                               double *frames, uint8_t *patches, fm3d_describe_stats *stats);
 
 /* ---------------- several GPUs of one node, one process ---------------- */
 /* The reference runs main.cpp:91-155 in one process on one device; these calls are the same
