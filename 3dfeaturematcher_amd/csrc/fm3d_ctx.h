@@ -167,7 +167,7 @@ struct fm3d_ctx {
     DevBuf orbPyr, orbTab, orbLev, orbMap, orbFlag, orbPos, orbKp, orbR, orbBlur, orbDesc, orbPat;
     std::vector<int> orbUserPattern;  // fm3d_orb_set_pattern (empty: makeRandomPattern(orbPatchSize))
     // the patch path's offset table (launch_orb_offset_table): 512 (dx, dy), the pattern, patch size and
-    // keypoint angle it was built from, and its largest |offset| + 3 (0: no table; orb_patch_prepare)
+    // keypoint angle it was built from, and its largest |offset| + 3 (0: no table; fm3d_patchdesc.cpp)
     DevBuf orbOffTab;
     std::vector<int> orbTabPattern;
     int orbTabPatchSize = 0, orbTabReach = 0;
@@ -204,12 +204,14 @@ struct fm3d_ctx {
     // the verified ones
     DevBuf verWork, verMatches;
     // fm3d_pipeline_describe (fm3d_tail.cpp): per point the frame, R, t and descriptor row; one chunk of
-    // patches; the per-patch constant tables of tailCap patches of edge tailSize (centred keypoint of
-    // angle tailAngle, SiftLevel rows, level indices), the SIFT blur taps of tailSigma and the
-    // oriented path's kept sum
-    DevBuf tailFrames, tailRT, tailDesc, tailPatch, tailKp, tailGL, tailLvl, tailTaps, tailSum;
-    int tailCap = 0, tailSize = 0, tailNTaps = 0;
-    float tailAngle = 0.f, tailSigma = 0.f;
+    // patches (the one-shot patch descriptors borrow the last two)
+    DevBuf tailFrames, tailRT, tailDesc, tailPatch;
+    // the patch describer (fm3d_patchdesc.cpp): the per-patch constant tables of pdCap patches of edge
+    // pdSize (centred keypoint of angle pdAngle, SiftLevel rows, level indices), the SIFT blur taps of
+    // pdSigma and the oriented path's kept count
+    DevBuf pdKp, pdGL, pdLvl, pdTaps, pdKept;
+    int pdCap = 0, pdSize = 0, pdNTaps = 0;
+    float pdAngle = 0.f, pdSigma = 0.f;
     // pinned staging: descriptors A / B (padded rows), keypoints, images, small tables, results
     HostBuf hA, hB, hK1, hK2, hImg, hTab, hProj, hSmall, hFlag;
     HostBuf hVer;  // a verified submit's fm3d::VerifySmall, stored by launch_verify_report
@@ -304,24 +306,6 @@ struct MatchOpts {
     int crossCheck = 0;
 };
 int run_match(fm3d_ctx* c, int nA, int nB, int type, int dimPad, const MatchOpts& o);
-
-// ---- fm3d_features.cpp: what fm3d_pipeline_describe shares with the one-shot patch descriptors
-int surf_patch_gws(int size);                    // the centred patch keypoint's wavelet size, 2 * round(2 s)
-int ensure_surf_dw(fm3d_ctx* c);                 // c->sfDW: SURF's 20 x 20 Gaussian, uploaded once
-const fm3d::SurfOri& surf_ori_samples();         // SURFInvoker's orientation disc
-// sift_patches' checks and its level-0 blur taps (sigma -> sig_diff)
-int sift_patch_taps(fm3d_ctx* c, std::vector<float>& taps);
-// ORB on patches of one edge, before any launch: orb_check_settings, the keep rule (FM3D_ERR_INVALID "ORB
-// drops the first patch's keypoint..."), the offset table of the centred keypoint (built on first use
-// and after a change of pattern, orbPatchSize or angle; the only wait) and launch_orb_patch_desc's
-// border guard against the table's own reach
-int orb_patch_prepare(fm3d_ctx* c, int size);
-// m patches on the device -> m x 32 bytes on the device, queued on the context stream
-void orb_patch_describe(fm3d_ctx* c, const uint8_t* patchesDev, int m, int size, uint8_t* rowsDev);
-// the border BRISK's and FREAK's compute demand around a keypoint of this size: brisk::size_of of its
-// scale, freak::pattern().sizes of its scale
-int brisk_border(float kpSize);
-int freak_border(float kpSize);
 
 // ---- fm3d_tail.cpp
 int describe_chunk();  // patches per chunk: the constant, or FM3D_DESCRIBE_CHUNK clamped to 1 .. 65535
