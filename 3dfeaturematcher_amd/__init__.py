@@ -55,6 +55,8 @@ EXPORTS = (
     "fm3d_pipeline_wait_dlt_verified",
     "fm3d_pipeline_describe",
     "fm3d_pipeline_describe_any", "fm3d_patch_keypoint_kept", "fm3d_patch_keypoint_kept_for",
+    "fm3d_align_points", "fm3d_match_models", "fm3d_ransac_sample3", "fm3d_rigid_from3", "fm3d_rigid_count",
+    "fm3d_rigid_refit",
 )
 
 # include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
@@ -200,6 +202,12 @@ class VerifyReport(ctypes.Structure):
         d["E"] = np.array(self.E, dtype=np.float64).reshape(3, 3)
         d["g12"] = np.array(self.g12, dtype=np.float64).reshape(4, 4)
         return d
+
+
+class AlignOpts(ctypes.Structure):
+    """fm3d_align_opts (fm3d_align_points / fm3d_match_models)."""
+    _fields_ = [("hypotheses", ctypes.c_int32), ("refineIters", ctypes.c_int32), ("maxDist", ctypes.c_double),
+                ("minNormalCos", ctypes.c_double), ("seed", ctypes.c_uint64)]
 
 
 def _verified_submit_argtypes(L) -> None:
@@ -1586,6 +1594,164 @@ def pose_from_epipolar(E, x1, x2, baseline: float = 1.0):
     if rc < 0:
         _check(rc)
     return g.reshape(4, 4), votes, rc == 0
+
+
+def _xyz(x, n=None):
+    a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f"expected {n} points, got {a.shape[0]}")
+    return a
+
+
+def _normal_pair(na, nb, a, b):
+    """both normal arrays, shaped like their points, or neither (fm3d_rigid_count's rule)"""
+    if (na is None) != (nb is None):
+        raise Fm3dError(ERR_INVALID, "normals: both arrays or neither")
+    if na is None:
+        return None, None
+    return _xyz(na, a.shape[0]), _xyz(nb, b.shape[0])
+
+
+def ransac_sample3(seed: int, h: int, M: int):
+    """fm3d_ransac_sample3: the three distinct match indices of hypothesis h among M matches (host only)
+    -> (idx (3,) int32, valid)."""
+    idx = np.zeros(3, dtype=np.int32)
+    rc = lib().fm3d_ransac_sample3(ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_int(h), ctypes.c_int(M),
+                                   _ptr(idx, ctypes.c_int32))
+    if rc < 0:
+        _check(rc)
+    return idx, rc == 0
+
+
+def rigid_from3(a, b):
+    """fm3d_rigid_from3: the rigid transform b = R a + t of three pairs of 3D points (host only)
+    -> (model (12,): R row-major, then t; valid); an invalid model is zero."""
+    pa, pb = _xyz(a, 3), _xyz(b, 3)
+    m = np.zeros(12)
+    rc = lib().fm3d_rigid_from3(_ptr(pa), _ptr(pb), _ptr(m))
+    if rc < 0:
+        _check(rc)
+    return m, rc == 0
+
+
+def rigid_count(model, a, b, max_dist: float, normals_a=None, normals_b=None, min_normal_cos: float = 0.0):
+    """fm3d_rigid_count: the pairs within max_dist of the model and, with normals, facing within
+    min_normal_cos (host only) -> (count, mask (n,) bool)."""
+    pa, pb = _xyz(a), _xyz(b)
+    if pa.shape != pb.shape:
+        raise ValueError("a and b differ in length")
+    na, nb = _normal_pair(normals_a, normals_b, pa, pb)
+    mask = np.zeros(max(pa.shape[0], 1), dtype=np.uint8)
+    rc = lib().fm3d_rigid_count(_ptr(np.ascontiguousarray(model, dtype=np.float64).ravel()), _ptr(pa), _ptr(pb), _vp(na),
+                                _vp(nb), pa.shape[0], ctypes.c_double(float(max_dist)),
+                                ctypes.c_double(float(min_normal_cos)), _ptr(mask, ctypes.c_uint8))
+    if rc < 0:
+        _check(rc)
+    return rc, mask[:pa.shape[0]].astype(bool)
+
+
+def rigid_refit(model, a, b, max_dist: float, normals_a=None, normals_b=None, min_normal_cos: float = 0.0,
+                sums: bool = False):
+    """fm3d_rigid_refit: the least-squares rigid transform of the pairs the model accepts (host only)
+    -> (model' (12,), valid); an invalid refit is zero.  sums: also the 7 + 9 sums of its two passes."""
+    pa, pb = _xyz(a), _xyz(b)
+    if pa.shape != pb.shape:
+        raise ValueError("a and b differ in length")
+    na, nb = _normal_pair(normals_a, normals_b, pa, pb)
+    out, S = np.zeros(12), np.zeros(16)
+    rc = lib().fm3d_rigid_refit(_ptr(np.ascontiguousarray(model, dtype=np.float64).ravel()), _ptr(pa), _ptr(pb), _vp(na),
+                                _vp(nb), pa.shape[0], ctypes.c_double(float(max_dist)),
+                                ctypes.c_double(float(min_normal_cos)), _ptr(out), _ptr(S))
+    if rc < 0:
+        _check(rc)
+    return (out, rc == 0, S) if sums else (out, rc == 0)
+
+
+class ModelAligner:
+    """3D-3D alignment of two feature models: a RANSAC fit of a rigid transform
+    b = R a + t to matched points (fm3d_record points, or any (n, 3) doubles), optionally tested on the
+    surface normals too, with a refit of the best model on the pairs it accepts."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+
+    @staticmethod
+    def _opts(max_dist, min_normal_cos, hypotheses, seed, refine) -> AlignOpts:
+        """fm3d_align_opts' rules, before the library is called"""
+        d, mc, H, R = float(max_dist), float(min_normal_cos), int(hypotheses), int(refine)
+        if not (d > 0.0 and d != float("inf")):
+            raise Fm3dError(ERR_INVALID, "maxDist must be finite and > 0")
+        if not -1.0 <= mc <= 1.0:
+            raise Fm3dError(ERR_INVALID, "minNormalCos must be in -1 .. 1")
+        if H < 1:
+            raise Fm3dError(ERR_INVALID, "hypotheses must be >= 1")
+        if not 0 <= R <= 16:
+            raise Fm3dError(ERR_INVALID, "refine must be in 0 .. 16")
+        return AlignOpts(H, R, d, mc, int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    @staticmethod
+    def _outputs(K, o, debug):
+        H, R = o.hypotheses, o.refineIters
+        return dict(g=np.zeros(16), mask=np.zeros(max(K, 1), dtype=np.uint8), out=np.zeros(max(K, 1), dtype=DMATCH),
+                    n=ctypes.c_int(0), best=ctypes.c_int(-1), counts=np.zeros(H, dtype=np.int32) if debug else None,
+                    models=np.zeros((H, 12)) if debug else None,
+                    rc=np.zeros(R + 1, dtype=np.int32) if debug and R else None,
+                    rm=np.zeros((max(R, 1), 12)) if debug and R else None, adopted=ctypes.c_int(0))
+
+    @staticmethod
+    def _tail(b):
+        return (_ptr(b["g"]), _ptr(b["mask"], ctypes.c_uint8), _vp(b["out"]), ctypes.byref(b["n"]), ctypes.byref(b["best"]),
+                _vp(b["counts"]), _vp(b["models"]), _vp(b["rc"]), _vp(b["rm"]), ctypes.byref(b["adopted"]))
+
+    @staticmethod
+    def _result(b, K, o, debug):
+        res = (b["g"].reshape(4, 4), b["mask"][:K].astype(bool), b["out"][:b["n"].value].copy(), b["best"].value)
+        if debug:
+            res += (b["counts"], b["models"])
+            if o.refineIters:
+                res += (b["rc"], b["rm"], b["adopted"].value)
+        return res
+
+    def align(self, pts_a, pts_b, matches, max_dist, normals_a=None, normals_b=None, min_normal_cos: float = 0.0,
+              hypotheses: int = 1024, seed: int = 0, refine: int = 0, debug: bool = False):
+        """fm3d_align_points: `hypotheses` three-point models scored against every match within max_dist
+        (the points' unit) and, with normals, (R n_a) . n_b >= min_normal_cos -> (g (4, 4) = [R | t],
+        mask (K,) bool, inliers (DMATCH, input order), best); with debug also counts (H,) int32 (-1 for
+        an invalid hypothesis) and models (H, 12: R row-major, then t).  No valid model: a zero g, no
+        inliers, best -1.  refine (0 .. 16): that many rounds of a least-squares refit on the pairs the
+        model accepts, each adopted iff valid and no worse in count; with refine > 0 and debug three
+        more: roundCounts (refine + 1,) int32 (c_0, then each round's count: -1 an invalid refit, -2 a
+        round not run), roundModels (refine, 12) and the number of rounds adopted."""
+        o = self._opts(max_dist, min_normal_cos, hypotheses, seed, refine)
+        a, b = _xyz(pts_a), _xyz(pts_b)
+        na, nb = _normal_pair(normals_a, normals_b, a, b)
+        m = np.ascontiguousarray(matches, dtype=DMATCH)
+        K = m.shape[0]
+        buf = self._outputs(K, o, debug)
+        self.ctx.check(lib().fm3d_align_points(self.ctx.handle, _vp(a), _vp(na), a.shape[0], _vp(b), _vp(nb), b.shape[0],
+                                               _vp(m), K, ctypes.byref(o), *self._tail(buf)))
+        return self._result(buf, K, o, debug)
+
+    def match_and_align(self, desc_a, desc_b, pts_a, pts_b, epsilon, max_dist, normals_a=None, normals_b=None,
+                        min_normal_cos: float = 0.0, hypotheses: int = 1024, seed: int = 0, refine: int = 0,
+                        debug: bool = False, binary: bool = False):
+        """fm3d_match_models: the context's matcher (NNDR at epsilon; the settings' crossCheck is
+        honoured) on one descriptor row per point, then align() on its matches without a trip through
+        the host -> (matches (DMATCH),) + align()'s result."""
+        o = self._opts(max_dist, min_normal_cos, hypotheses, seed, refine)
+        da, db = np.ascontiguousarray(desc_a), np.ascontiguousarray(desc_b)
+        a, b = _xyz(pts_a, da.shape[0]), _xyz(pts_b, db.shape[0])
+        na, nb = _normal_pair(normals_a, normals_b, a, b)
+        nA = da.shape[0]
+        matches = np.zeros(max(nA, 1), dtype=DMATCH)
+        nm = ctypes.c_int(0)
+        buf = self._outputs(nA, o, debug)
+        self.ctx.check(lib().fm3d_match_models(self.ctx.handle, _vp(da), _vp(a), _vp(na), nA, _vp(db), _vp(b), _vp(nb),
+                                               db.shape[0], da.shape[1], _desc_type(da, binary),
+                                               ctypes.c_double(float(epsilon)), ctypes.byref(o), _vp(matches),
+                                               ctypes.byref(nm), *self._tail(buf)))
+        K = nm.value
+        return (matches[:K].copy(),) + self._result(buf, K, o, debug)
 
 
 class MOSAIC:

@@ -375,6 +375,31 @@ size_t verify_pose_bytes();
 void launch_verify_pose(int M, const double* xy, const int* flag, const int* best, const double* E, void* work,
                         double** cand, int** valid, int** votes, hipStream_t s);
 
+// ---------------- 3D-3D alignment (fm3d_align.hip) ----------------
+// the two models' points (and normals: both or neither) on the device, n x 3 doubles each
+struct AlignIn {
+    const double *ptsA, *nrmA, *ptsB, *nrmB;
+    int nA, nB;
+};
+// planes of verify_pad(M) doubles that launch_align fills: a (3), b (3), then the normals' (3 + 3)
+inline int align_planes(bool normals) { return normals ? 12 : 6; }
+// The whole stage on device inputs, queued on s: the matched coordinates gathered into `planes`
+// (align_planes() x verify_pad(M) doubles, NaN in the pad and for a match index outside its array), H
+// hypotheses (models H x 12, count H: -1 for an invalid one), their scores, the best (best, model[12]:
+// -1 and zeros when none is valid) and its inlier mask (flag M ints for the compaction, mask M bytes).
+// M >= 3, 1 <= H <= kVerifyMaxHyps.
+void launch_align(const AlignIn& in, const fm3d_dmatch* matches, int M, int H, unsigned long long seed, double tau2,
+                  double minCos, int nCU, double* planes, double* models, int* count, int* best, double* model,
+                  int* flag, uint8_t* mask, hipStream_t s, bool withMask = true);
+// The refinement after launch_align(..., withMask = false): `rounds` (1 .. 16) refits of the model on the
+// pairs it accepts, each adopted iff valid and no worse in count, all queued on s without a host sync,
+// then the mask of the final model.  work: align_refine_bytes(M, rounds), 8-byte aligned; the three
+// outputs point into it: roundCounts (rounds + 1 ints), roundModels (rounds x 12), adopted (1 int).
+size_t align_refine_bytes(int M, int rounds);
+void launch_align_refine(int M, bool normals, int rounds, double tau2, double minCos, const double* planes,
+                         const int* count, const int* best, double* model, void* work, int* flag, uint8_t* mask,
+                         int** roundCounts, double** roundModels, int** adopted, hipStream_t s);
+
 // ---------------- triangulation ----------------
 struct TriParams {
     Camera cam;

@@ -373,6 +373,71 @@ int fm3d_epipolar_count(const double E[9], const double *x1, const double *x2, i
 int fm3d_pose_from_epipolar(const double E[9], const double *x1, const double *x2, int n, double baseline,
                             double g12[16], int32_t votes[4]);
 
+/* ---------------- 3D-3D alignment of two feature models ---------------- */
+typedef struct fm3d_align_opts {
+    int32_t hypotheses;     /* 1 .. 2^20 */
+    int32_t refineIters;    /* 0 .. 16 rounds of the refit */
+    double maxDist;         /* finite, > 0, in the points' unit */
+    double minNormalCos;    /* -1 .. 1; read only when normals are given */
+    uint64_t seed;
+} fm3d_align_opts;
+/* RANSAC fit of a rigid transform b = R a + t to matched 3D points (no reference counterpart: its
+   mosaic.cpp computeImpl is empty).  ptsA / ptsB: nA / nB x 3 doubles, e.g. fm3d_record points of two
+   models; nrmA / nrmB: their unit normals, both given or both NULL; matches: queryIdx into A,
+   trainIdx into B.  Hypothesis h = 0 .. hypotheses-1 takes the three matches
+   fm3d_ransac_sample3(seed, h, nMatches) names, fits fm3d_rigid_from3 to them and counts the matches
+   fm3d_rigid_count accepts: |R a + t - b| <= maxDist and, with normals, (R n_a) . n_b >= minNormalCos.
+   The best is the largest count, the lowest h on ties; then refineIters rounds of fm3d_rigid_refit on
+   the pairs the current model accepts, adopted and reported as fm3d_verify_matches_refined's rounds are
+   (roundCounts refineIters + 1 int32, roundModels refineIters x 12, *roundsAdopted; may be NULL).
+   g: the row-major 4 x 4 [R | t; 0 0 0 1] of the final model; inlierMask: nMatches bytes; inliers
+   (capacity nMatches): the input matches it accepts, in their order; *best: the RANSAC's index.
+   nMatches < 3 or no valid hypothesis: *best = -1, g zero, no inliers, FM3D_OK.  counts (hypotheses
+   int32, -1 for an invalid hypothesis) and models (hypotheses x 12: R row-major, then t) may be NULL.
+   refineIters == 0 gives the unrefined result byte for byte.  Results depend on the inputs and the
+   seed alone (no floating-point atomics).  One scoped device allocation per call.
+   FM3D_ERR_INVALID, before any launch: a null required pointer, only one of the two normal arrays,
+   hypotheses < 1, maxDist not finite or not > 0, minNormalCos outside [-1, 1] or NaN, refineIters
+   outside 0 .. 16, a match index outside [0, nA) / [0, nB); FM3D_ERR_UNSUPPORTED: more than 2^20
+   hypotheses. */
+int fm3d_align_points(fm3d_ctx *ctx, const double *ptsA, const double *nrmA, int nA, const double *ptsB,
+                      const double *nrmB, int nB, const fm3d_dmatch *matches, int nMatches,
+                      const fm3d_align_opts *opts, double g[16], uint8_t *inlierMask, fm3d_dmatch *inliers,
+                      int *nInliers, int *best, int32_t *counts, double *models, int32_t *roundCounts,
+                      double *roundModels, int *roundsAdopted);
+/* The context's matcher and the alignment in one call: fm3d_match_nndr (fm3d_match_mutual with the
+   settings' crossCheck as its mode when that is 1 or 2; guidedMatchPx is ignored: there is no image
+   geometry) of descA / descB (nA / nB rows of dim, type as fm3d_knn2), then fm3d_align_points on those
+   matches where they lie on the device: one host wait for the match count.  matches (capacity nA)
+   and *nMatches: the matcher's; inlierMask and inliers have capacity nA.  Every output equals the two
+   calls', byte for byte.  The refusals are both calls'. */
+int fm3d_match_models(fm3d_ctx *ctx, const void *descA, const double *ptsA, const double *nrmA, int nA,
+                      const void *descB, const double *ptsB, const double *nrmB, int nB, int dim, int type,
+                      double epsilon, const fm3d_align_opts *opts, fm3d_dmatch *matches, int *nMatches, double g[16],
+                      uint8_t *inlierMask, fm3d_dmatch *inliers, int *nInliers, int *best, int32_t *counts,
+                      double *models, int32_t *roundCounts, double *roundModels, int *roundsAdopted);
+/* The alignment's algebra on the host (no context, usable without a GPU), the code the kernels run.
+   A model is twelve doubles: R row-major, then t.
+   fm3d_ransac_sample3: the three distinct indices in [0, M) of hypothesis h, the first three distinct
+   values of fm3d_ransac_sample's draws in their order; returns 1 (idx partly -1) when 64 draws give
+   fewer, as every M < 3 does.
+   fm3d_rigid_from3: the model of three pairs (a, b: 3 x (x, y, z)) -- centroids, the 3 x 3 cross matrix,
+   its two leading singular pairs, the third by cross products; returns 1 and a zero model when invalid
+   (a second singular value <= DBL_MIN: collinear or coincident points; a non-finite number).
+   fm3d_rigid_count: the number of the n pairs within maxDist of the model and, when na and nb are
+   given, with (R n_a) . n_b >= minNormalCos; mask (n bytes) may be NULL.
+   fm3d_rigid_refit: the least-squares model of the pairs `model` accepts, in two passes of sums in the
+   order of DESIGN.md §3.1d (tiles of 1,024 pairs, a balanced tree inside a tile, tiles in order):
+   the centroids, then the centred cross matrix; returns 1 and a zero model when invalid (fewer than
+   three pairs in, a non-finite sum, fm3d_rigid_from3's reasons).  sums (may be NULL): the 7 + 9 sums.
+   FM3D_ERR_INVALID: a null pointer, only one of na / nb, a negative h, M or n. */
+int fm3d_ransac_sample3(uint64_t seed, int h, int M, int32_t idx[3]);
+int fm3d_rigid_from3(const double a[9], const double b[9], double model[12]);
+int fm3d_rigid_count(const double model[12], const double *a, const double *b, const double *na, const double *nb,
+                     int n, double maxDist, double minNormalCos, uint8_t *mask);
+int fm3d_rigid_refit(const double model[12], const double *a, const double *b, const double *na, const double *nb,
+                     int n, double maxDist, double minNormalCos, double out[12], double sums[16]);
+
 /* ---------------- NormalOptimizer ---------------- */
 /* setImages (normaloptimizer.cpp:191-221): 8-bit gray images, builds both pyramids */
 int fm3d_set_images(fm3d_ctx *ctx, const uint8_t *img1, const uint8_t *img2, int width, int height, int stride);

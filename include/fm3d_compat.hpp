@@ -432,6 +432,39 @@ private:
     fm3d_lm_stats stats_{};
 };
 
+// 3D-3D alignment of two feature models (no reference counterpart): the rigid
+// transform b = R a + t, row-major [R | t; 0 0 0 1], that a RANSAC over `hypotheses` three-point models
+// finds for the matched points (queryIdx into pointsA, trainIdx into pointsB) within maxDist, refitted
+// refineIters times (0 .. 16) on the pairs it accepts; all zero when no model is valid.  inliers
+// (optional) is cleared then filled with the matches the final model accepts, in input order.  With both
+// normal vectors given a pair must also have (R n_a) . n_b >= minNormalCos.
+inline Matx44d alignModels(Device& d, const std::vector<Vec3d>& pointsA, const std::vector<Vec3d>& pointsB,
+                           const std::vector<DMatch>& matches, double maxDist, std::vector<DMatch>* inliers = nullptr,
+                           int hypotheses = 1024, uint64_t seed = 0, int refineIters = 0,
+                           const std::vector<Vec3d>* normalsA = nullptr, const std::vector<Vec3d>* normalsB = nullptr,
+                           double minNormalCos = 0.0) {
+    if ((normalsA && normalsA->size() != pointsA.size()) || (normalsB && normalsB->size() != pointsB.size()))
+        throw Error(FM3D_ERR_INVALID, "alignModels: one normal per point");
+    const int K = (int)matches.size();
+    std::vector<uint8_t> mask(K > 0 ? K : 1);
+    std::vector<DMatch> kept(K > 0 ? K : 1);
+    const fm3d_align_opts o{hypotheses, refineIters, maxDist, minNormalCos, seed};
+    Matx44d g;
+    int n = 0, best = -1;
+    // (std::array<double, 3> is three contiguous doubles: a vector of them is the ABI's n x 3 array)
+    check(d.ctx(), fm3d_align_points(d.ctx(), pointsA.empty() ? nullptr : pointsA[0].data(),
+                                     normalsA && !normalsA->empty() ? (*normalsA)[0].data() : nullptr, (int)pointsA.size(),
+                                     pointsB.empty() ? nullptr : pointsB[0].data(),
+                                     normalsB && !normalsB->empty() ? (*normalsB)[0].data() : nullptr, (int)pointsB.size(),
+                                     matches.data(), K, &o, g.data(), mask.data(), kept.data(), &n, &best, nullptr,
+                                     nullptr, nullptr, nullptr, nullptr));
+    if (inliers) {
+        kept.resize(n);
+        inliers->swap(kept);
+    }
+    return g;
+}
+
 }  // namespace compat
 }  // namespace fm3d
 
