@@ -57,6 +57,7 @@ EXPORTS = (
     "fm3d_pipeline_describe_any", "fm3d_patch_keypoint_kept", "fm3d_patch_keypoint_kept_for",
     "fm3d_align_points", "fm3d_match_models", "fm3d_ransac_sample3", "fm3d_rigid_from3", "fm3d_rigid_count",
     "fm3d_rigid_refit",
+    "fm3d_localize_points", "fm3d_localize_model", "fm3d_quartic_roots", "fm3d_p3p", "fm3d_pnp_count", "fm3d_pnp_step",
 )
 
 # include/fm3d.h's FM3D_PROBE_* table by position (fm3d_math_probe), and its functions of two arguments
@@ -208,6 +209,12 @@ class AlignOpts(ctypes.Structure):
     """fm3d_align_opts (fm3d_align_points / fm3d_match_models)."""
     _fields_ = [("hypotheses", ctypes.c_int32), ("refineIters", ctypes.c_int32), ("maxDist", ctypes.c_double),
                 ("minNormalCos", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
+class LocalizeOpts(ctypes.Structure):
+    """fm3d_localize_opts (fm3d_localize_points / fm3d_localize_model)."""
+    _fields_ = [("samples", ctypes.c_int32), ("refineIters", ctypes.c_int32), ("maxPx", ctypes.c_double),
+                ("minFacingCos", ctypes.c_double), ("seed", ctypes.c_uint64)]
 
 
 def _verified_submit_argtypes(L) -> None:
@@ -1752,6 +1759,145 @@ class ModelAligner:
                                                ctypes.byref(nm), *self._tail(buf)))
         K = nm.value
         return (matches[:K].copy(),) + self._result(buf, K, o, debug)
+
+
+def quartic_roots(coef):
+    """fm3d_quartic_roots: the real roots of coef[4] x^4 + .. + coef[0] (host only) -> (roots (4,): NaN
+    where a position holds none, their number, valid)."""
+    c = np.ascontiguousarray(coef, dtype=np.float64).ravel()
+    if c.shape[0] != 5:
+        raise ValueError("expected five coefficients")
+    roots, n = np.zeros(4), ctypes.c_int(0)
+    rc = lib().fm3d_quartic_roots(_ptr(c), _ptr(roots), ctypes.byref(n))
+    if rc < 0:
+        _check(rc)
+    return roots, n.value, rc == 0
+
+
+def p3p(X, uv):
+    """fm3d_p3p: the up to four poses Xc = R X + t of three model points X (3, 3) seen at the normalised
+    image points uv (3, 2) (host only) -> (models (4, 12): R row-major, then t, zero when invalid;
+    valid (4,) bool)."""
+    px = _xyz(X, 3)
+    pu = np.ascontiguousarray(uv, dtype=np.float64).reshape(3, 2)
+    m, ok = np.zeros((4, 12)), np.zeros(4, dtype=np.int32)
+    rc = lib().fm3d_p3p(_ptr(px), _ptr(pu), _ptr(m), _ptr(ok, ctypes.c_int32))
+    if rc < 0:
+        _check(rc)
+    return m, ok.astype(bool)
+
+
+def _uv_xyz(uv, X, normals):
+    pu = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+    px = _xyz(X, pu.shape[0])
+    return pu, px, None if normals is None else _xyz(normals, pu.shape[0])
+
+
+def pnp_count(model, uv, X, tau: float, normals=None, min_facing_cos: float = 0.0):
+    """fm3d_pnp_count: the matches whose point reprojects within tau (normalised units) of its image
+    point in front of the camera and, with normals, faces it within min_facing_cos (host only)
+    -> (count, mask (n,) bool)."""
+    pu, px, pn = _uv_xyz(uv, X, normals)
+    mask = np.zeros(max(pu.shape[0], 1), dtype=np.uint8)
+    rc = lib().fm3d_pnp_count(_ptr(np.ascontiguousarray(model, dtype=np.float64).ravel()), _ptr(pu), _ptr(px), _vp(pn),
+                              pu.shape[0], ctypes.c_double(float(tau)), ctypes.c_double(float(min_facing_cos)),
+                              _ptr(mask, ctypes.c_uint8))
+    if rc < 0:
+        _check(rc)
+    return rc, mask[:pu.shape[0]].astype(bool)
+
+
+def pnp_step(model, uv, X, tau: float, normals=None, min_facing_cos: float = 0.0, sums: bool = False):
+    """fm3d_pnp_step: one Gauss-Newton step of the reprojection error on the matches the model accepts
+    (host only) -> (model' (12,), valid); an invalid step is zero.  sums: also its 28 sums."""
+    pu, px, pn = _uv_xyz(uv, X, normals)
+    out, S = np.zeros(12), np.zeros(28)
+    rc = lib().fm3d_pnp_step(_ptr(np.ascontiguousarray(model, dtype=np.float64).ravel()), _ptr(pu), _ptr(px), _vp(pn),
+                             pu.shape[0], ctypes.c_double(float(tau)), ctypes.c_double(float(min_facing_cos)), _ptr(out),
+                             _ptr(S))
+    if rc < 0:
+        _check(rc)
+    return (out, rc == 0, S) if sums else (out, rc == 0)
+
+
+class ModelLocalizer:
+    """2D-3D localisation of an image against a feature model: a RANSAC fit of the
+    camera pose Xc = R X + t to matches between the model's points (fm3d_record points, or any (n, 3)
+    doubles) and the image's keypoints, optionally tested on the model's normals too, with a
+    Gauss-Newton refit of the best pose on the matches it accepts.  Uses the camera of the context's
+    settings."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+
+    @staticmethod
+    def _opts(max_px, min_facing_cos, samples, seed, refine) -> LocalizeOpts:
+        """fm3d_localize_opts' rules, before the library is called"""
+        _check_max_px(max_px)
+        mc, S, R = float(min_facing_cos), int(samples), int(refine)
+        if not 0.0 <= mc <= 1.0:
+            raise Fm3dError(ERR_INVALID, "minFacingCos must be in 0 .. 1")
+        if S < 1:
+            raise Fm3dError(ERR_INVALID, "samples must be >= 1")
+        if not 0 <= R <= 16:
+            raise Fm3dError(ERR_INVALID, "refine must be in 0 .. 16")
+        return LocalizeOpts(S, R, float(max_px), mc, int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    @staticmethod
+    def _outputs(K, o, debug):
+        H, R = 4 * o.samples, o.refineIters
+        return dict(g=np.zeros(16), mask=np.zeros(max(K, 1), dtype=np.uint8), out=np.zeros(max(K, 1), dtype=DMATCH),
+                    n=ctypes.c_int(0), best=ctypes.c_int(-1), counts=np.zeros(H, dtype=np.int32) if debug else None,
+                    models=np.zeros((H, 12)) if debug else None,
+                    rc=np.zeros(R + 1, dtype=np.int32) if debug and R else None,
+                    rm=np.zeros((max(R, 1), 12)) if debug and R else None, adopted=ctypes.c_int(0))
+
+    def localize(self, pts, kpts, matches, max_px, normals=None, min_facing_cos: float = 0.0, samples: int = 256,
+                 seed: int = 0, refine: int = 0, debug: bool = False):
+        """fm3d_localize_points: `samples` three-match samples of up to four P3P poses each, scored against
+        every match within max_px pixels and, with normals, facing the camera within min_facing_cos
+        -> (g (4, 4) = [R | t], model frame to camera frame; mask (K,) bool; inliers (DMATCH, input
+        order); best); with debug also counts (4 * samples,) int32 (-1 for an invalid hypothesis) and
+        models (4 * samples, 12: R row-major, then t).  matches: queryIdx into kpts, trainIdx into pts.
+        No valid model: a zero g, no inliers, best -1.  refine (0 .. 16): that many rounds of a
+        Gauss-Newton step on the matches the model accepts, each adopted iff valid and no worse in
+        count; with refine > 0 and debug three more: roundCounts (refine + 1,) int32 (c_0, then each
+        round's count: -1 an invalid step, -2 a round not run), roundModels (refine, 12) and the number
+        of rounds adopted."""
+        o = self._opts(max_px, min_facing_cos, samples, seed, refine)
+        X = _xyz(pts)
+        n = None if normals is None else _xyz(normals, X.shape[0])
+        kp = np.ascontiguousarray(kpts, dtype=np.float32).reshape(-1, 2)
+        m = np.ascontiguousarray(matches, dtype=DMATCH)
+        K = m.shape[0]
+        buf = self._outputs(K, o, debug)
+        self.ctx.check(lib().fm3d_localize_points(self.ctx.handle, _vp(X), _vp(n), X.shape[0], _vp(kp), kp.shape[0], _vp(m),
+                                                  K, ctypes.byref(o), *ModelAligner._tail(buf)))
+        return ModelAligner._result(buf, K, o, debug)
+
+    def match_and_localize(self, desc_img, kpts, desc_model, pts, epsilon, max_px, normals=None,
+                           min_facing_cos: float = 0.0, samples: int = 256, seed: int = 0, refine: int = 0,
+                           debug: bool = False, binary: bool = False):
+        """fm3d_localize_model: the context's matcher (NNDR at epsilon; the settings' crossCheck is
+        honoured) with the image's descriptor rows as queries and the model's as train, then localize()
+        on its matches without a trip through the host -> (matches (DMATCH),) + localize()'s result."""
+        o = self._opts(max_px, min_facing_cos, samples, seed, refine)
+        di, dm = np.ascontiguousarray(desc_img), np.ascontiguousarray(desc_model)
+        X = _xyz(pts, dm.shape[0])
+        n = None if normals is None else _xyz(normals, X.shape[0])
+        kp = np.ascontiguousarray(kpts, dtype=np.float32).reshape(-1, 2)
+        nK = di.shape[0]
+        if kp.shape[0] != nK:
+            raise ValueError(f"expected {nK} keypoints, got {kp.shape[0]}")
+        matches = np.zeros(max(nK, 1), dtype=DMATCH)
+        nm = ctypes.c_int(0)
+        buf = self._outputs(nK, o, debug)
+        self.ctx.check(lib().fm3d_localize_model(self.ctx.handle, _vp(di), _vp(kp), nK, _vp(dm), _vp(X), _vp(n), X.shape[0],
+                                                 di.shape[1], _desc_type(di, binary), ctypes.c_double(float(epsilon)),
+                                                 ctypes.byref(o), _vp(matches), ctypes.byref(nm),
+                                                 *ModelAligner._tail(buf)))
+        K = nm.value
+        return (matches[:K].copy(),) + ModelAligner._result(buf, K, o, debug)
 
 
 class MOSAIC:

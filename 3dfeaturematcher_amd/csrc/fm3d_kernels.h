@@ -400,6 +400,36 @@ void launch_align_refine(int M, bool normals, int rounds, double tau2, double mi
                          const int* count, const int* best, double* model, void* work, int* flag, uint8_t* mask,
                          int** roundCounts, double** roundModels, int** adopted, hipStream_t s);
 
+// ---------------- 2D-3D localisation (fm3d_localize.hip) ----------------
+// the image's keypoints and the model's points (and normals, or null) on the device
+struct LocalizeIn {
+    const fm3d_point2f* kpts;
+    const double *pts, *nrm;
+    int nKpts, nPts;
+};
+// planes of verify_pad(M) doubles that launch_localize fills: u v (the keypoint through undistort1),
+// X (3), then the normal (3)
+inline int localize_planes(bool normals) { return normals ? 8 : 5; }
+// The whole stage on device inputs, queued on s: the matched values gathered into `planes`
+// (localize_planes() x verify_pad(M) doubles, NaN in the pad and for a match index outside its array),
+// H = 4 x samples hypotheses (models H x 12, count H: -1 for an invalid one; 4 h + k is slot k of
+// sample h), their scores, the best (best, model[12]: -1 and zeros when none is valid) and its inlier
+// mask (flag M ints for the compaction, mask M bytes).  cos2: minFacingCos squared.
+// M >= 3, 1 <= H <= kVerifyMaxHyps.
+void launch_localize(const Camera& cam, const LocalizeIn& in, const fm3d_dmatch* matches, int M, int samples,
+                     unsigned long long seed, double tau2, double cos2, int nCU, double* planes, double* models,
+                     int* count, int* best, double* model, int* flag, uint8_t* mask, hipStream_t s,
+                     bool withMask = true);
+// The refinement after launch_localize(..., withMask = false): `rounds` (1 .. 16) Gauss-Newton steps of
+// the model on the matches it accepts, each adopted iff valid and no worse in count, all queued on s
+// without a host sync, then the mask of the final model.  work: localize_refine_bytes(M, rounds), 8-byte
+// aligned; the three outputs point into it: roundCounts (rounds + 1 ints), roundModels (rounds x 12),
+// adopted (1 int).
+size_t localize_refine_bytes(int M, int rounds);
+void launch_localize_refine(int M, bool normals, int rounds, double tau2, double cos2, const double* planes,
+                            const int* count, const int* best, double* model, void* work, int* flag, uint8_t* mask,
+                            int** roundCounts, double** roundModels, int** adopted, hipStream_t s);
+
 // ---------------- triangulation ----------------
 struct TriParams {
     Camera cam;

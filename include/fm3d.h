@@ -438,6 +438,78 @@ int fm3d_rigid_count(const double model[12], const double *a, const double *b, c
 int fm3d_rigid_refit(const double model[12], const double *a, const double *b, const double *na, const double *nb,
                      int n, double maxDist, double minNormalCos, double out[12], double sums[16]);
 
+/* ---------------- 2D-3D localisation of an image against a feature model ---------------- */
+typedef struct fm3d_localize_opts {
+    int32_t samples;        /* 1 .. 2^18 (x 4 models each) */
+    int32_t refineIters;    /* 0 .. 16 rounds of the refit */
+    double maxPx;           /* finite, > 0, in pixels */
+    double minFacingCos;    /* 0 .. 1; read only when normals are given */
+    uint64_t seed;
+} fm3d_localize_opts;
+/* RANSAC fit of the camera pose Xc = R X + t to matches between a model's 3D points and an image's
+   keypoints (no reference counterpart; needs the camera of the context's settings, not g12).  pts: nPts
+   x 3 doubles, e.g. fm3d_record points; nrm: their unit normals or NULL; kpts: the image's nKpts
+   keypoints in pixels; matches: queryIdx into kpts (the image), trainIdx into pts (the model).  Sample
+   h = 0 .. samples-1 takes the three matches fm3d_ransac_sample3(seed, h, nMatches) names and solves
+   fm3d_p3p on their points and undistorted normalised keypoints (kept as doubles): up to four models,
+   hypothesis 4 h + k being slot k.  Every hypothesis counts the matches fm3d_pnp_count accepts within
+   maxPx pixels (the unit of fm3d_verify_matches: tau = maxPx * 2 / (Fx + Fy)) and, with normals, facing
+   within minFacingCos.  The best is the largest count, the lowest index on ties; then refineIters rounds
+   of fm3d_pnp_step on the matches the current model accepts, adopted and reported as
+   fm3d_align_points' rounds are (roundCounts refineIters + 1 int32, roundModels refineIters x 12,
+   *roundsAdopted; may be NULL).  g: the row-major 4 x 4 [R | t; 0 0 0 1] of the final model, model frame
+   to camera frame: for a model in camera 1's frame and an image of camera 2 it is the g12 that
+   fm3d_set_g12 installs.  inlierMask: nMatches bytes; inliers (capacity nMatches): the input matches
+   it accepts, in their order; *best: the RANSAC's index.  nMatches < 3 or no valid hypothesis:
+   *best = -1, g zero, no inliers, FM3D_OK.  counts (4 x samples int32, -1 for an invalid hypothesis) and
+   models (4 x samples x 12: R row-major, then t; zero when invalid) may be NULL.  refineIters == 0 gives
+   the unrefined result byte for byte.  Results depend on the inputs and the seed alone (no
+   floating-point atomics).  One scoped device allocation per call, one wait.
+   FM3D_ERR_INVALID, before any launch: a null required pointer, samples < 1, maxPx not finite or not
+   > 0, minFacingCos outside [0, 1] or NaN, refineIters outside 0 .. 16, a match index outside
+   [0, nKpts) / [0, nPts); FM3D_ERR_UNSUPPORTED: more than 2^18 samples. */
+int fm3d_localize_points(fm3d_ctx *ctx, const double *pts, const double *nrm, int nPts, const fm3d_point2f *kpts,
+                         int nKpts, const fm3d_dmatch *matches, int nMatches, const fm3d_localize_opts *opts,
+                         double g[16], uint8_t *inlierMask, fm3d_dmatch *inliers, int *nInliers, int *best,
+                         int32_t *counts, double *models, int32_t *roundCounts, double *roundModels,
+                         int *roundsAdopted);
+/* The context's matcher and the localisation in one call: fm3d_match_nndr (fm3d_match_mutual with the
+   settings' crossCheck as its mode when that is 1 or 2; guidedMatchPx is ignored: the pose is what is
+   sought) of descImg (nKpts query rows) against descModel (nPts train rows; dim, type as fm3d_knn2),
+   then fm3d_localize_points on those matches where they lie on the device: one host wait for the
+   match count.  matches (capacity nKpts) and *nMatches: the matcher's; inlierMask and inliers have
+   capacity nKpts.  Every output equals the two calls', byte for byte.  The refusals are both calls'. */
+int fm3d_localize_model(fm3d_ctx *ctx, const void *descImg, const fm3d_point2f *kpts, int nKpts,
+                        const void *descModel, const double *pts, const double *nrm, int nPts, int dim, int type,
+                        double epsilon, const fm3d_localize_opts *opts, fm3d_dmatch *matches, int *nMatches,
+                        double g[16], uint8_t *inlierMask, fm3d_dmatch *inliers, int *nInliers, int *best,
+                        int32_t *counts, double *models, int32_t *roundCounts, double *roundModels,
+                        int *roundsAdopted);
+/* The localisation's algebra on the host (no context, usable without a GPU), the code the kernels run
+   (include/fm3d_pnp.h).  uv: normalised undistorted image points, n x 2; X: model points, n x 3; nrm:
+   their normals or NULL; tau in normalised units.
+   fm3d_quartic_roots: the real roots of coef[4] x^4 + .. + coef[0] by Ferrari's method (a bisected
+   resolvent root, two quadratics, two Newton steps each) in four fixed positions, NaN where there is
+   none; *nRoots (may be NULL) their number; returns 1 when |coef[4]| is not > DBL_MIN or a monic
+   coefficient is not finite.
+   fm3d_p3p: the up to four poses of three matches (X: 3 x 3, uv: 3 x 2) by elimination to a quartic
+   in the ratio of two distances; models: 4 x 12, slot k belonging to root position k, zero when
+   invalid; valid (may be NULL): 4 flags; returns the number of valid slots.
+   fm3d_pnp_count: the number of the n matches with z > 0 and (x - u z)^2 + (y - v z)^2 <= tau^2 z^2 for
+   (x, y, z) = R X + t and, with nrm, d = (R n) . Xc >= 0 and d^2 >= minFacingCos^2 |Xc|^2; mask (n
+   bytes) may be NULL.
+   fm3d_pnp_step: one Gauss-Newton step of the reprojection error over the matches `model` accepts --
+   28 sums in the order of DESIGN.md §3.1d (J^T J's upper triangle, J^T r, the count), a 6 x 6 Cholesky
+   solve, the rotation updated by the Cayley map; returns 1 and a zero model when invalid (fewer than
+   three matches in, a non-finite sum, a pivot not > 0).  sums (may be NULL): the 28.
+   FM3D_ERR_INVALID: a null pointer, a negative n. */
+int fm3d_quartic_roots(const double coef[5], double roots[4], int *nRoots);
+int fm3d_p3p(const double X[9], const double uv[6], double models[48], int32_t valid[4]);
+int fm3d_pnp_count(const double model[12], const double *uv, const double *X, const double *nrm, int n, double tau,
+                   double minFacingCos, uint8_t *mask);
+int fm3d_pnp_step(const double model[12], const double *uv, const double *X, const double *nrm, int n, double tau,
+                  double minFacingCos, double out[12], double sums[28]);
+
 /* ---------------- NormalOptimizer ---------------- */
 /* setImages (normaloptimizer.cpp:191-221): 8-bit gray images, builds both pyramids */
 int fm3d_set_images(fm3d_ctx *ctx, const uint8_t *img1, const uint8_t *img2, int width, int height, int stride);

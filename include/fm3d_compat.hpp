@@ -465,6 +465,38 @@ inline Matx44d alignModels(Device& d, const std::vector<Vec3d>& pointsA, const s
     return g;
 }
 
+// 2D-3D localisation of an image against a feature model (no reference counterpart):
+// the camera pose Xc = R X + t, row-major [R | t; 0 0 0 1], that a RANSAC over `samples` three-match
+// samples (up to four P3P poses each) finds for the matches (queryIdx into keypoints, trainIdx into
+// points) within maxPx pixels under the device's camera, refitted refineIters times (0 .. 16) on the
+// matches it accepts; all zero when no model is valid.  For a model in camera 1's frame and an image of
+// camera 2 the result is the g12 that setg12 would install.  inliers (optional) is cleared then filled
+// with the matches the final model accepts, in input order.  With normals given a match must also face
+// the camera within minFacingCos.
+inline Matx44d localizeImage(Device& d, const std::vector<Vec3d>& points, const std::vector<KeyPoint>& keypoints,
+                             const std::vector<DMatch>& matches, double maxPx, std::vector<DMatch>* inliers = nullptr,
+                             int samples = 256, uint64_t seed = 0, int refineIters = 0,
+                             const std::vector<Vec3d>* normals = nullptr, double minFacingCos = 0.0) {
+    if (normals && normals->size() != points.size()) throw Error(FM3D_ERR_INVALID, "localizeImage: one normal per point");
+    const int K = (int)matches.size();
+    std::vector<uint8_t> mask(K > 0 ? K : 1);
+    std::vector<DMatch> kept(K > 0 ? K : 1);
+    std::vector<fm3d_point2f> kp(keypoints.size());
+    for (size_t i = 0; i < keypoints.size(); i++) kp[i] = fm3d_point2f{keypoints[i].pt.x, keypoints[i].pt.y};
+    const fm3d_localize_opts o{samples, refineIters, maxPx, minFacingCos, seed};
+    Matx44d g;
+    int n = 0, best = -1;
+    check(d.ctx(), fm3d_localize_points(d.ctx(), points.empty() ? nullptr : points[0].data(),
+                                        normals && !normals->empty() ? (*normals)[0].data() : nullptr, (int)points.size(),
+                                        kp.empty() ? nullptr : kp.data(), (int)kp.size(), matches.data(), K, &o, g.data(),
+                                        mask.data(), kept.data(), &n, &best, nullptr, nullptr, nullptr, nullptr, nullptr));
+    if (inliers) {
+        kept.resize(n);
+        inliers->swap(kept);
+    }
+    return g;
+}
+
 }  // namespace compat
 }  // namespace fm3d
 
