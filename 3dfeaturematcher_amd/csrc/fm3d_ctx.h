@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -18,6 +19,35 @@ namespace fm3d_host {
 // DeviceMem (hipMalloc) or PinnedMem (hipHostMalloc).  ensure() grows only, and frees the old block
 // before it allocates the new one.  hipFree and hipHostFree synchronise the device first, so a block
 // that queued work still names outlives that work -- when ensure() grows as at scope exit.
+//
+// Test hook FM3D_DEBUG_POISON (tests/test_gpu_poison.py): when set, its value (strtoul, base 0) is a
+// 32-bit word that fills every newly allocated block -- whole words and the tail bytes -- before
+// ensure() returns, so a read of memory nothing wrote changes the result the same way every run.
+// Read at each allocation; unset, it costs that one getenv.
+inline bool poison_word(uint32_t* word) {
+    const char* e = getenv("FM3D_DEBUG_POISON");
+    if (!e || !e[0]) return false;
+    *word = (uint32_t)strtoul(e, nullptr, 0);
+    return true;
+}
+// the tail bytes continue the word's little-endian byte pattern
+inline void poison_host(void* p, size_t n, uint32_t word) {
+    uint8_t* b = (uint8_t*)p;
+    for (size_t i = 0; i < n; i++) b[i] = (uint8_t)(word >> (8 * (i & 3)));
+}
+// A device block: filled on the null stream, then the device is synchronised -- the contexts'
+// streams are non-blocking, so the null stream alone orders nothing before their work.
+inline hipError_t poison_device(void* p, size_t n) {
+    uint32_t word;
+    if (!poison_word(&word)) return hipSuccess;
+    hipError_t e = hipSuccess;
+    if (n / 4) e = hipMemsetD32((hipDeviceptr_t)p, (int)word, n / 4);
+    for (size_t i = n & ~(size_t)3; e == hipSuccess && i < n; i++)
+        e = hipMemset((uint8_t*)p + i, (int)(uint8_t)(word >> (8 * (i & 3))), 1);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    return e;
+}
+
 template <class Mem>
 struct Buf {
     void* p = nullptr;
@@ -49,7 +79,13 @@ struct Buf {
         bytes = 0;
         size_t alloc = n < Mem::kMin ? Mem::kMin : n;
         hipError_t e = Mem::alloc(&p, alloc);
-        if (e == hipSuccess) bytes = alloc;
+        if (e == hipSuccess) e = Mem::poison(p, alloc);
+        if (e == hipSuccess) {
+            bytes = alloc;
+        } else if (p) {
+            Mem::free(p);
+            p = nullptr;
+        }
         return e;
     }
     template <typename T>
@@ -62,6 +98,7 @@ struct DeviceMem {
     static constexpr size_t kMin = 256;
     static hipError_t alloc(void** p, size_t n) { return hipMalloc(p, n); }
     static hipError_t free(void* p) { return hipFree(p); }
+    static hipError_t poison(void* p, size_t n) { return poison_device(p, n); }
 };
 // page-locked host staging: the H2D copies of the inputs run asynchronously from it, at full PCIe
 // rate, and the host may return before they execute (fm3d_pipeline_submit)
@@ -69,6 +106,11 @@ struct PinnedMem {
     static constexpr size_t kMin = 4096;
     static hipError_t alloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
     static hipError_t free(void* p) { return hipHostFree(p); }
+    static hipError_t poison(void* p, size_t n) {  // on the host: nothing is queued on a new block
+        uint32_t word;
+        if (poison_word(&word)) poison_host(p, n, word);
+        return hipSuccess;
+    }
 };
 using DevBuf = Buf<DeviceMem>;
 using HostBuf = Buf<PinnedMem>;

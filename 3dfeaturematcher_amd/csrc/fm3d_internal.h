@@ -26,3 +26,6 @@ int fm3d_internal_prepare(fm3d_ctx* c);
 // its LM slabs (the largest launch) + a conservative estimate of the per-pair buffers
 int fm3d_internal_memory_need(fm3d_ctx* c, int64_t nA, int64_t nB, int dim, int type, int width, int height,
                               size_t* bytes);
+// Test probe of FM3D_DEBUG_POISON (tests/test_gpu_poison.py; C linkage, so that ctypes finds it): a
+// fresh local DevBuf of `bytes` bytes (> 0), ensured and copied back to out with nothing written
+extern "C" int fm3d_internal_alloc_probe(fm3d_ctx* c, size_t bytes, uint8_t* out);

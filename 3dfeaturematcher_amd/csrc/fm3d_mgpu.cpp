@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "fm3d.h"
+#include "fm3d_ctx.h"
 #include "fm3d_internal.h"
 
 namespace {
@@ -255,6 +256,10 @@ int plan(fm3d_mgpu* m, int64_t nA, int64_t nB, int dim, int type, int width, int
                 MHIP(m, hipMalloc(&m->send[k][d], slot));
                 MHIP(m, hipMalloc(&m->recv[k][d], slot * m->ndev));
                 MHIP(m, hipMalloc((void**)&m->cntRecv[k][d], sizeof(int32_t) * m->ndev));
+                // as Buf::ensure does for the contexts' blocks (FM3D_DEBUG_POISON)
+                MHIP(m, fm3d_host::poison_device(m->send[k][d], slot));
+                MHIP(m, fm3d_host::poison_device(m->recv[k][d], slot * m->ndev));
+                MHIP(m, fm3d_host::poison_device(m->cntRecv[k][d], sizeof(int32_t) * m->ndev));
             }
         m->capDev = cap;
     }

@@ -783,6 +783,15 @@ int fm3d_internal_memory_need(fm3d_ctx* c, int64_t nA, int64_t nB, int dim, int 
     return FM3D_OK;
 }
 
+int fm3d_internal_alloc_probe(fm3d_ctx* c, size_t bytes, uint8_t* out) {
+    if (!c || !bytes || !out) return fail(c, FM3D_ERR_INVALID, "alloc_probe: null context, no bytes or null out");
+    hipSetDevice(c->device);
+    DevBuf b;
+    HIPCHK(c, b.ensure(bytes));
+    HIPCHK(c, hipMemcpy(out, b.p, bytes, hipMemcpyDeviceToHost));
+    return FM3D_OK;
+}
+
 int fm3d_internal_prepare(fm3d_ctx* c) {  // the device count buffer, before a collective names it
     hipSetDevice(c->device);
     HIPCHK(c, c->pcnt.ensure(64));
