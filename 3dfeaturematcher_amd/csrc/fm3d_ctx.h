@@ -115,7 +115,12 @@ struct PinnedMem {
 using DevBuf = Buf<DeviceMem>;
 using HostBuf = Buf<PinnedMem>;
 
+// (the LM gathers read a level's row-major bytes up to offset (h + 1) w + w + 1 < h w + kGuard(w))
 constexpr size_t kGuard(int w) { return (size_t)4 * w + 64; }
+// image 2's column-major level copies (LevelDesc::img2t): (w + 2) columns of stride kColStride(h),
+// rows y >= h of every column and the bytes past the last column zero
+constexpr int kColStride(int h) { return (h + 2 + 63) / 64 * 64; }
+constexpr size_t kColBytes(int w, int h) { return (size_t)(w + 2) * kColStride(h) + 64; }
 
 // the pipeline's small device -> host results of one frame pair (one D2H, pinned)
 struct PipeSmall {
@@ -187,6 +192,8 @@ struct fm3d_ctx {
     int w = 0, h = 0;
     std::vector<int> lw, lh;
     std::vector<DevBuf> pyr1, pyr2;
+    std::vector<DevBuf> pyr2t;  // image 2's levels column-major (kColStride), for the LM gathers
+    int lmCols = -1;            // the last LM launch's image-2 layout: 1 columns, 0 rows
     int pyrGuardW = -1, pyrGuardH = -1, pyrGuardLevels = -1;  // the geometry whose guards are zero
     DevBuf lvlDesc;
     // circle offsets of pixelsRay

@@ -17,6 +17,7 @@
 
 #include "fm3d.h"
 #include "fm3d_ctx.h"
+#include "fm3d_internal.h"
 #include "fm3d_kernels.h"
 
 using fm3d::LevelDesc;
@@ -133,6 +134,7 @@ int set_images_impl(fm3d_ctx* c, const uint8_t* img1, const uint8_t* img2, int w
     c->lh.assign(levels + 1, 0);
     c->pyr1.resize(levels + 1);
     c->pyr2.resize(levels + 1);
+    c->pyr2t.resize(levels + 1);
     c->lw[0] = width;
     c->lh[0] = height;
     for (int L = 1; L <= levels; L++) {  // cv::pyrDown size ((w+1)/2, (h+1)/2)
@@ -148,9 +150,11 @@ int set_images_impl(fm3d_ctx* c, const uint8_t* img1, const uint8_t* img2, int w
         size_t bytes = (size_t)c->lw[L] * c->lh[L] + kGuard(c->lw[L]);
         void* p1 = c->pyr1[L].p;
         void* p2 = c->pyr2[L].p;
+        void* pt = c->pyr2t[L].p;
         HIPCHK(c, c->pyr1[L].ensure(bytes));
         HIPCHK(c, c->pyr2[L].ensure(bytes));
-        fresh |= c->pyr1[L].p != p1 || c->pyr2[L].p != p2;
+        HIPCHK(c, c->pyr2t[L].ensure(kColBytes(c->lw[L], c->lh[L])));
+        fresh |= c->pyr1[L].p != p1 || c->pyr2[L].p != p2 || c->pyr2t[L].p != pt;
     }
     for (int L = 0; fresh && L <= levels; L++) {
         // a level's pixels are overwritten (level 0 by the copy below, the others by pyrDown): the
@@ -158,6 +162,9 @@ int set_images_impl(fm3d_ctx* c, const uint8_t* img1, const uint8_t* img2, int w
         const size_t img = (size_t)c->lw[L] * c->lh[L];
         HIPCHK(c, hipMemsetAsync((char*)c->pyr1[L].p + img, 0, c->pyr1[L].bytes - img, c->stream));
         HIPCHK(c, hipMemsetAsync((char*)c->pyr2[L].p + img, 0, c->pyr2[L].bytes - img, c->stream));
+        // the column-major copy's guard cells lie between its columns: the whole buffer (the copy's
+        // writers touch the same cells for every frame pair of this geometry)
+        HIPCHK(c, hipMemsetAsync(c->pyr2t[L].p, 0, c->pyr2t[L].bytes, c->stream));
     }
     c->pyrGuardW = width;
     c->pyrGuardH = height;
@@ -170,16 +177,20 @@ int set_images_impl(fm3d_ctx* c, const uint8_t* img1, const uint8_t* img2, int w
     }
     HIPCHK(c, hipMemcpyAsync(c->pyr1[0].p, c->hImg.p, wh, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->pyr2[0].p, c->hImg.as<uint8_t>() + wh, wh, hipMemcpyHostToDevice, c->stream));
+    fm3d::launch_level_transpose(c->pyr2[0].as<uint8_t>(), width, height, c->pyr2t[0].as<uint8_t>(), kColStride(height),
+                                 c->stream);
     for (int L = 1; L <= levels; L++) {
         fm3d::launch_pyrdown(c->pyr1[L - 1].as<uint8_t>(), c->lw[L - 1], c->lh[L - 1], c->pyr1[L].as<uint8_t>(),
                              c->stream);
         fm3d::launch_pyrdown(c->pyr2[L - 1].as<uint8_t>(), c->lw[L - 1], c->lh[L - 1], c->pyr2[L].as<uint8_t>(),
-                             c->stream);
+                             c->stream, c->pyr2t[L].as<uint8_t>(), kColStride(c->lh[L]));
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, c->hTab.ensure((levels + 1) * sizeof(LevelDesc)));
     LevelDesc* d = c->hTab.as<LevelDesc>();
-    for (int L = 0; L <= levels; L++) d[L] = LevelDesc{c->pyr1[L].as<uint8_t>(), c->pyr2[L].as<uint8_t>(), c->lw[L], c->lh[L]};
+    for (int L = 0; L <= levels; L++)
+        d[L] = LevelDesc{c->pyr1[L].as<uint8_t>(), c->pyr2[L].as<uint8_t>(), c->lw[L], c->lh[L],
+                         c->pyr2t[L].as<uint8_t>(), kColStride(c->lh[L])};
     HIPCHK(c, c->lvlDesc.ensure((levels + 1) * sizeof(LevelDesc)));
     HIPCHK(c, hipMemcpyAsync(c->lvlDesc.p, d, (levels + 1) * sizeof(LevelDesc), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->evStage, c->stream));
@@ -375,6 +386,20 @@ int fm3d_get_pyramid_level(const fm3d_ctx* cc, int which, int level, uint8_t* ou
     }
     return FM3D_OK;
 }
+
+int fm3d_internal_level_cols(fm3d_ctx* c, int level, uint8_t* out, int* w, int* h, int* hs, size_t* bytes) {
+    if (!c || level < 0 || level >= (int)c->pyr2t.size()) return FM3D_ERR_INVALID;
+    hipSetDevice(c->device);
+    const size_t n = kColBytes(c->lw[level], c->lh[level]);
+    if (w) *w = c->lw[level];
+    if (h) *h = c->lh[level];
+    if (hs) *hs = kColStride(c->lh[level]);
+    if (bytes) *bytes = n;
+    if (out) HIPCHK(c, hipMemcpy(out, c->pyr2t[level].p, n, hipMemcpyDeviceToHost));
+    return FM3D_OK;
+}
+
+int fm3d_internal_lm_img2_cols(const fm3d_ctx* c) { return c ? c->lmCols : -1; }
 
 int fm3d_records_download(fm3d_ctx* c, const fm3d_record* recordsDev, int n, fm3d_record* out) {
     if (!c || n < 0 || (n && !out)) return FM3D_ERR_INVALID;

@@ -29,3 +29,10 @@ int fm3d_internal_memory_need(fm3d_ctx* c, int64_t nA, int64_t nB, int dim, int 
 // Test probe of FM3D_DEBUG_POISON (tests/test_gpu_poison.py; C linkage, so that ctypes finds it): a
 // fresh local DevBuf of `bytes` bytes (> 0), ensured and copied back to out with nothing written
 extern "C" int fm3d_internal_alloc_probe(fm3d_ctx* c, size_t bytes, uint8_t* out);
+// Test accessors of the LM's image-2 layout (tests/test_gpu_lm_img2_layout.py; C linkage).
+// The column-major copy of image 2's pyramid level with its guard: *w, *h the level's size, *hs the
+// column stride, *bytes = (w + 2) hs + the guard past the last column; out (may be null) takes them
+extern "C" int fm3d_internal_level_cols(fm3d_ctx* c, int level, uint8_t* out, int* w, int* h, int* hs,
+                                        size_t* bytes);
+// the layout the context's last LM launch read image 2 in: 1 columns, 0 rows, -1 no launch yet
+extern "C" int fm3d_internal_lm_img2_cols(const fm3d_ctx* c);

@@ -22,6 +22,10 @@ struct LevelDesc {
     const uint8_t* img1;  // pyramid level of image 1 (+ zero guard)
     const uint8_t* img2;
     int w, h;
+    // column-major copy of image 2's level for the LM gathers ("Gather geometry"):
+    // T(x, y) = img2[y * w + x] at img2t[x * hs + y], 0 <= x <= w + 1, 0 <= y <= h + 1 (+ zero guard)
+    const uint8_t* img2t;
+    int hs;
 };
 
 // camera-2 projection constants (projectPointsToImage2, singlecameratriangulator.cpp:591-644)
@@ -101,7 +105,8 @@ constexpr int kLM2Ring = 8;  // chunks of 64 entries in flight per slot
 constexpr int kLM2Threads = 64 * (kLM2Slots + 1);
 // MULTI: the problems' ProjConst entries differ (per-pass pose offset); false: entry 0 for all.
 // TREE: the tree-summed reduction mode (kLM2Slots + 1 term waves, no chain wave)
-template <bool MULTI, bool TREE>
+// COLS: the image-2 gathers read the levels' column-major copies (LevelDesc::img2t), else the rows
+template <bool MULTI, bool TREE, bool COLS>
 __global__ void lm2_kernel(LMParams p);
 
 // ---------------- matching ----------------
@@ -512,7 +517,10 @@ void launch_triangulate_compact(const TriParams& p, double* out, int* srcIdx, in
 int triangulate_compact_blocks(int K);
 
 // ---------------- images ----------------
-void launch_pyrdown(const uint8_t* src, int w, int h, uint8_t* dst, hipStream_t s);
+// dstT (may be null): the destination level's column-major copy of stride hs, written with it
+void launch_pyrdown(const uint8_t* src, int w, int h, uint8_t* dst, hipStream_t s, uint8_t* dstT = nullptr, int hs = 0);
+// level 0's column-major copy from its row-major pixels
+void launch_level_transpose(const uint8_t* src, int w, int h, uint8_t* dstT, int hs, hipStream_t s);
 void launch_undistort(const Camera& cam, const double* xy, int n, double* out, hipStream_t s);
 
 // ---------------- the shared math headers, element-wise (fm3d_probe.hip) ----------------

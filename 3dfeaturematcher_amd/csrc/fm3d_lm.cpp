@@ -1,5 +1,6 @@
 // fm3d_lm.cpp -- the host side of the LM normals (fm3d_lm2.hip): the launch over one or several
 // frame pairs' points (run_lm, run_lm_multi: the pipeline's too) and fm3d_optimize_normals.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -81,6 +82,29 @@ int lm_groups(fm3d_ctx* c, const void* kptr, int slots, long Ptot, long* out) {
     return FM3D_OK;
 }
 
+// Whether image 1's y axis maps closer to image 2's y axis than to its x axis under q's camera-2
+// pose: the projections (no distortion) of the mid-depth points on the rays through image 1's
+// principal point and through the pixel below it.  The 64 lanes of an LM chunk are 64 consecutive
+// rows of one image-1 column (ensure_offsets: x outer, y inner), so their image-2 samples then run
+// down a column and the column-major level copy serves them from 1-3 cache lines (DESIGN.md §3.4,
+// "Gather geometry"); a pair rolled by about 90 degrees keeps the rows.
+bool lm_prefers_cols(const fm3d_ctx* q) {
+    const fm3d::Camera& k = q->cam;
+    const double z = 0.5 * (q->s.zThresholdMin + q->s.zThresholdMax);
+    const double X[2][3] = {{0., 0., z}, {0., z / k.fy, z}};
+    double u[2], v[2];
+    for (int i = 0; i < 2; i++) {
+        const double* R = q->R2;
+        const double x = R[0] * X[i][0] + R[1] * X[i][1] + R[2] * X[i][2] + q->t2[0];
+        const double y = R[3] * X[i][0] + R[4] * X[i][1] + R[5] * X[i][2] + q->t2[1];
+        const double w = R[6] * X[i][0] + R[7] * X[i][1] + R[8] * X[i][2] + q->t2[2];
+        if (!(w > 0.)) return false;
+        u[i] = k.fx * x / w;
+        v[i] = k.fy * y / w;
+    }
+    return std::fabs(v[1] - v[0]) > std::fabs(u[1] - u[0]);  // false for NaN
+}
+
 // LM normals over the points of nProb frame pairs in ONE launch on c's stream (c's slabs, queue
 // and launch counters): the slots that find one pair's points used up take the next pair's, so
 // a second pair fills the launch's end-of-queue tail (fm3d_pipeline_link).  Every problem's
@@ -125,10 +149,27 @@ int run_lm_multi(fm3d_ctx* c, const LMSrc* src, int nProb, fm3d_lm_stats* stats,
     for (int j = 1; j < nProb; j++)
         multiPose |= std::memcmp(src[j].c->R2, src[0].c->R2, sizeof(c->R2)) != 0 ||
                      std::memcmp(src[j].c->t2, src[0].c->t2, sizeof(c->t2)) != 0;
-    const void* kptr = tree ? (multiPose ? reinterpret_cast<const void*>(fm3d::lm2_kernel<true, true>)
-                                         : reinterpret_cast<const void*>(fm3d::lm2_kernel<false, true>))
-                            : (multiPose ? reinterpret_cast<const void*>(fm3d::lm2_kernel<true, false>)
-                                         : reinterpret_cast<const void*>(fm3d::lm2_kernel<false, false>));
+    // image 2's layout for the gathers: the columns only if every pair's pose chooses them.
+    // FM3D_LM_IMG2 = rows | cols | auto (default) forces one: the results are the same bits (tests, A/B)
+    bool cols = true;
+    for (int j = 0; j < nProb; j++) cols &= lm_prefers_cols(src[j].c);
+    if (const char* lay = getenv("FM3D_LM_IMG2")) {
+        if (!std::strcmp(lay, "rows")) cols = false;
+        else if (!std::strcmp(lay, "cols")) cols = true;
+        else if (std::strcmp(lay, "auto")) return fail(c, FM3D_ERR_INVALID, "FM3D_LM_IMG2 must be rows, cols or auto");
+    }
+    for (int j = 0; j < nProb; j++) src[j].c->lmCols = cols;
+    c->lmCols = cols;
+    const void* const kptrs[2][2][2] = {
+        {{reinterpret_cast<const void*>(fm3d::lm2_kernel<false, false, false>),
+          reinterpret_cast<const void*>(fm3d::lm2_kernel<false, false, true>)},
+         {reinterpret_cast<const void*>(fm3d::lm2_kernel<true, false, false>),
+          reinterpret_cast<const void*>(fm3d::lm2_kernel<true, false, true>)}},
+        {{reinterpret_cast<const void*>(fm3d::lm2_kernel<false, true, false>),
+          reinterpret_cast<const void*>(fm3d::lm2_kernel<false, true, true>)},
+         {reinterpret_cast<const void*>(fm3d::lm2_kernel<true, true, false>),
+          reinterpret_cast<const void*>(fm3d::lm2_kernel<true, true, true>)}}};
+    const void* kptr = kptrs[tree][multiPose][cols];  // [TREE][MULTI][COLS]
     long groups = 0;
     int r0;
     if ((r0 = lm_groups(c, kptr, slots, Ptot, &groups))) return r0;

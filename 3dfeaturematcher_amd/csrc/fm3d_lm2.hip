@@ -101,6 +101,9 @@ struct SlotP2 {
     double scale, xmax, ymax, ccx, ccy, ajn0s, tq, ajn1s, tq0, agiant, wF;
     const uint8_t* img1;
     const uint8_t* img2;
+    // COLS launches: the level's column-major copy of image 2 and its column stride (LevelDesc)
+    const uint8_t* img2t;
+    int s2;
 };
 
 // persistent bookkeeping state of a slot (lane 0 of its term wave only)
@@ -216,6 +219,8 @@ struct Ctl2 {
         P.img1 = lv.img1;
         P.img2 = lv.img2;
         P.lw = lv.w;
+        P.img2t = lv.img2t;
+        P.s2 = lv.hs;
         P.ccx = S.ccx;
         P.ccy = S.ccy;
     }
@@ -849,7 +854,9 @@ struct Geo2 {
 // MULTI: the launch's problems have different poses -- the pass's entry of the table (projOff,
 // one more scalar register live across the pass loops: +3-6 % cycles per evaluation pass,
 // measured); otherwise entry 0
-template <bool MMOK, bool MULTI>
+// COLS: the offset into the level's column-major copy (lw its column stride), x * lw + y, for the
+// rows' y * lw + x -- either way one v_mad_u32_u24
+template <bool MMOK, bool MULTI, bool COLS>
 __device__ __forceinline__ Geo2 geometry2(const LMParams& p, unsigned projOff, double ux, double uy, double n0,
                                           double n1, double n2, double mm, double scale,
                                           unsigned long long xmaxb, unsigned long long ymaxb, int lw, double cm) {
@@ -880,7 +887,8 @@ __device__ __forceinline__ Geo2 geometry2(const LMParams& p, unsigned projOff, d
              __ballot((unsigned long long)__double_as_longlong(v) <= ymaxb);
     r.fx = (float)(scale * u);
     r.fy = (float)(scale * v);
-    const unsigned o = __umul24((unsigned)(int)floorf(r.fy), (unsigned)lw) + (unsigned)(int)floorf(r.fx);
+    const unsigned o = COLS ? __umul24((unsigned)(int)floorf(r.fx), (unsigned)lw) + (unsigned)(int)floorf(r.fy)
+                            : __umul24((unsigned)(int)floorf(r.fy), (unsigned)lw) + (unsigned)(int)floorf(r.fx);
     r.off = sel_mask_u32(o, r.good);
     return r;
 }
@@ -896,10 +904,13 @@ __device__ __noinline__ int plane_code(double ux, double uy, double n0, double n
 
 // getBilinearInterpPix32f on the gathered window, the floors taken from the sample
 // coordinates (exact: |x| < 2^24 wherever the value is used)
+// COLS: the window gathered from the column-major copy -- lo = (x0; y0, y0 + 1), hi = (x0 + 1; ...):
+// the same four bytes, b01 and b10 from the other pair's byte
+template <bool COLS>
 __device__ __forceinline__ float bilinear_w(unsigned lo, unsigned hi, float x, float y) {
     const float x0 = floorf(x), y0 = floorf(y);
-    const float b00 = (float)(lo & 0xff), b01 = (float)((lo >> 8) & 0xff);
-    const float b10 = (float)(hi & 0xff), b11 = (float)((hi >> 8) & 0xff);
+    const float b00 = (float)(lo & 0xff), b01 = COLS ? (float)(hi & 0xff) : (float)((lo >> 8) & 0xff);
+    const float b10 = COLS ? (float)((lo >> 8) & 0xff) : (float)(hi & 0xff), b11 = (float)((hi >> 8) & 0xff);
     const float xm0 = 1.0f - (x - x0), xm1 = (x - x0);
     const float ym0 = 1.0f - (y - y0), ym1 = (y - y0);
     return xm0 * (b00 * ym0 + b10 * ym1) + xm1 * (b01 * ym0 + b11 * ym1);
@@ -909,9 +920,10 @@ __device__ __forceinline__ float bilinear_w(unsigned lo, unsigned hi, float x, f
 // (as two-lane float vectors: v_pk_mul_f32 / v_pk_add_f32 do the two columns' independent
 // products and sums, each rounded as the scalar operation; 11 instructions instead of 17)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <bool COLS>
 __device__ __forceinline__ float bilinear_f(unsigned lo, unsigned hi, float xf, float yf) {
-    const f32x2 b0 = {(float)(lo & 0xff), (float)((lo >> 8) & 0xff)};  // b00, b01
-    const f32x2 b1 = {(float)(hi & 0xff), (float)((hi >> 8) & 0xff)};  // b10, b11
+    const f32x2 b0 = {(float)(lo & 0xff), COLS ? (float)(hi & 0xff) : (float)((lo >> 8) & 0xff)};  // b00, b01
+    const f32x2 b1 = {COLS ? (float)((lo >> 8) & 0xff) : (float)(hi & 0xff), (float)((hi >> 8) & 0xff)};  // b10, b11
     const float ym0 = 1.0f - yf, ym1 = yf;
     const f32x2 sc = b0 * ym0 + b1 * ym1;  // (b00 ym0 + b10 ym1, b01 ym0 + b11 ym1)
     const f32x2 xm = {1.0f - xf, xf};
@@ -1067,7 +1079,7 @@ __device__ __noinline__ void chain_wave(int lane, unsigned long long tStart, lon
 }  // namespace
 
 // 4 waves per SIMD: one workgroup of 16 waves per CU (128 VGPRs)
-template <bool MULTI, bool TREE>
+template <bool MULTI, bool TREE, bool COLS>
 __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
     Shared& sh = g_sh;
     constexpr int NS = TREE ? kWA : kW;  // term waves (slots) of the workgroup
@@ -1292,8 +1304,10 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
                     const double scale = SP.scale;
                     const unsigned long long xmaxb = (unsigned long long)__double_as_longlong(SP.xmax);
                     const unsigned long long ymaxb = (unsigned long long)__double_as_longlong(SP.ymax);
-                    const uint8_t* img2 = SP.img2;
-                    const int lw = rfl(SP.lw);
+                    // image 2's level as the launch reads it: rows of lw = w bytes, or (COLS) the
+                    // column-major copy with lw its column stride
+                    const uint8_t* img2 = COLS ? SP.img2t : SP.img2;
+                    const int lw = rfl(COLS ? SP.s2 : SP.lw);
                     const unsigned projOff = MULTI ? (unsigned)rfl((int)SP.projOff) : 0u;
                     const bool i1ok = rfl(SS.i1ok) != 0;
                     const gu8* img2b = (const gu8*)rfl_ptr(img2);
@@ -1336,9 +1350,9 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
                             float i1;
                         };
                         auto geo = [&](double ux, double uy, double n0, double n1, double n2, double mm) {
-                            return FAST ? geometry2<true, MULTI>(p, projOff, ux, uy, n0, n1, n2, mm, scale, xmaxb,
+                            return FAST ? geometry2<true, MULTI, COLS>(p, projOff, ux, uy, n0, n1, n2, mm, scale, xmaxb,
                                                                  ymaxb, lw, cm)
-                                        : geometry2<false, MULTI>(p, projOff, ux, uy, n0, n1, n2, mm, scale, xmaxb,
+                                        : geometry2<false, MULTI, COLS>(p, projOff, ux, uy, n0, n1, n2, mm, scale, xmaxb,
                                                                   ymaxb, lw, cm);
                         };
                         auto jdiv = [&](double a, double h, double y, bool mok) {
@@ -1364,7 +1378,8 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
                             L.dF = JAC ? (double)__builtin_nontemporal_load((const gfloat*)(pc->slabDF + o4)) : 0.;
                             return L;
                         };
-                        auto gather = [&](unsigned off) {  // two byte pairs: (y0, x0..x0+1), (y0+1, ...)
+                        // two byte pairs: (y0, x0..x0+1), (y0+1, ...); COLS: (x0, y0..y0+1), (x0+1, ...)
+                        auto gather = [&](unsigned off) {
                             return make_uint2(*(const gu16u*)(img2b + off), *(const gu16u*)(img2b + (off + lw)));
                         };
                         auto chunk = [&](const Ld& L, int k, unsigned o4) {
@@ -1397,7 +1412,7 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
                                 }
                             }
                             // evaluateNormal :145-148 (fvec), fdjac2 forward differences (JAC)
-                            const float dI0 = L.i1 - bilinear_w(a.x, a.y, g0.fx, g0.fy);
+                            const float dI0 = L.i1 - bilinear_w<COLS>(a.x, a.y, g0.fx, g0.fy);
                             const double r0 = w0 * (double)dI0;
                             double v0 = JAC ? jdiv(r0 - wF * L.dF, h0, y0, mok0) : r0;
                             v0 = sel_mask(v0, ok & g0.good);
@@ -1409,7 +1424,7 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
                             const double t0 = enorm_term2(v0, agiant, slow0);
                             double v1 = 0., t1 = 0.;
                             if (NEV == 2) {
-                                const float dI1 = L.i1 - bilinear_w(c.x, c.y, g1.fx, g1.fy);
+                                const float dI1 = L.i1 - bilinear_w<COLS>(c.x, c.y, g1.fx, g1.fy);
                                 const double r1 = w1 * (double)dI1;
                                 v1 = jdiv(r1 - wF * L.dF, h1, y1, mok1);
                                 v1 = sel_mask(v1, ok & g1.good);
@@ -1472,8 +1487,8 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
                             };
                             auto back2 = [&](const St2& S, int k, unsigned oo) {
                                 // evaluateNormal :145-148, fdjac2 forward differences
-                                const float dI0 = S.i1 - bilinear_f(S.a.x, S.a.y, S.xf0, S.yf0);
-                                const float dI1 = S.i1 - bilinear_f(S.c.x, S.c.y, S.xf1, S.yf1);
+                                const float dI0 = S.i1 - bilinear_f<COLS>(S.a.x, S.a.y, S.xf0, S.yf0);
+                                const float dI1 = S.i1 - bilinear_f<COLS>(S.c.x, S.c.y, S.xf1, S.yf1);
                                 if constexpr (TREE) {
                                     // the columns' values and sums come from the Q_GRAM sweep
                                     const auto* pc = sb();
@@ -1575,7 +1590,7 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
                             // the residual / Jacobian value of one chunk of the stage (the samples wait
                             // for the stage's gathers)
                             auto value = [&](float xf, float yf, uint2 w, float i1, float dF, LaneMask ok, float& dI) {
-                                dI = i1 - bilinear_f(w.x, w.y, xf, yf);
+                                dI = i1 - bilinear_f<COLS>(w.x, w.y, xf, yf);
                                 const double r = w0 * (double)dI;
                                 const double v = JAC ? jdiv(r - wF * (double)dF, h0, y0, mok0) : r;
                                 return sel_mask(v, ok);
@@ -1660,7 +1675,7 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
                                 A = load(o8 + 2 * st8, o4 + 2 * st4);
                                 B = load(o8 + 3 * st8, o4 + 3 * st4);
                                 auto back1 = [&](const Geo2& g, uint2 w, float i1, double dF, LaneMask in, unsigned oo, int kk) {
-                                    const float dI = i1 - bilinear_w(w.x, w.y, g.fx, g.fy);
+                                    const float dI = i1 - bilinear_w<COLS>(w.x, w.y, g.fx, g.fy);
                                     const double r = w0 * (double)dI;
                                     double v = JAC ? jdiv(r - wF * dF, h0, y0, mok0) : r;
                                     v = sel_mask(v, (i1ok ? in : 0ull) & g.good);
@@ -2013,9 +2028,13 @@ __global__ __launch_bounds__(kLM2Threads, 4) void lm2_kernel(LMParams p) {
 
 // one pose for every problem of the launch (one frame pair, or linked pairs of one rig pose), and
 // a pose per problem
-template __global__ void lm2_kernel<false, false>(LMParams p);
-template __global__ void lm2_kernel<true, false>(LMParams p);
-template __global__ void lm2_kernel<false, true>(LMParams p);
-template __global__ void lm2_kernel<true, true>(LMParams p);
+template __global__ void lm2_kernel<false, false, false>(LMParams p);
+template __global__ void lm2_kernel<true, false, false>(LMParams p);
+template __global__ void lm2_kernel<false, true, false>(LMParams p);
+template __global__ void lm2_kernel<true, true, false>(LMParams p);
+template __global__ void lm2_kernel<false, false, true>(LMParams p);
+template __global__ void lm2_kernel<true, false, true>(LMParams p);
+template __global__ void lm2_kernel<false, true, true>(LMParams p);
+template __global__ void lm2_kernel<true, true, true>(LMParams p);
 
 }  // namespace fm3d

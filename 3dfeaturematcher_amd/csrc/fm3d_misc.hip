@@ -176,7 +176,29 @@ __device__ inline int reflect101(int q, int len) {
     return q;
 }
 
-__global__ void pyrdown_kernel(const uint8_t* __restrict__ src, int w, int h, uint8_t* __restrict__ dst) {
+// Pixel (x, y) = v of a w-wide level into the level's column-major copy T of stride hs, where
+// T(x', y') = flat[y' * w + x'] for 0 <= x' <= w + 1 (flat: the row-major level with its zero
+// guard): the pixel itself and, past the row's end, its places as "the next row's first bytes".
+// Every other cell of T is guard (zero, never written).
+__device__ inline void store_colmajor(uint8_t* __restrict__ T, int hs, int w, int x, int y, uint8_t v) {
+    T[(size_t)x * hs + y] = v;
+    for (int xx = x + w, yy = y - 1; xx <= w + 1 && yy >= 0; xx += w, yy--) T[(size_t)xx * hs + yy] = v;
+}
+
+// level 0's column-major copy: 32 x 32 tiles through LDS (rows read, columns written, both contiguous)
+__global__ void level_transpose_kernel(const uint8_t* __restrict__ src, int w, int h, uint8_t* __restrict__ dstT,
+                                       int hs) {
+    __shared__ uint8_t tile[32][33];
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int sx = blockIdx.x * 32 + tx, sy = blockIdx.y * 32 + ty;
+    if (sx < w && sy < h) tile[ty][tx] = src[(size_t)sy * w + sx];
+    __syncthreads();
+    const int x = blockIdx.x * 32 + ty, y = blockIdx.y * 32 + tx;
+    if (x < w && y < h) store_colmajor(dstT, hs, w, x, y, tile[tx][ty]);
+}
+
+__global__ void pyrdown_kernel(const uint8_t* __restrict__ src, int w, int h, uint8_t* __restrict__ dst,
+                               uint8_t* __restrict__ dstT, int hs) {
     const int dw = (w + 1) / 2, dh = (h + 1) / 2;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y * blockDim.y + threadIdx.y;
@@ -191,7 +213,9 @@ __global__ void pyrdown_kernel(const uint8_t* __restrict__ src, int w, int h, ui
         for (int j = 0; j < 5; j++) rs += wt[j] * row[sx[j]];
         s += wt[i] * rs;
     }
-    dst[(size_t)y * dw + x] = (uint8_t)((s + 128) >> 8);
+    const uint8_t v = (uint8_t)((s + 128) >> 8);
+    dst[(size_t)y * dw + x] = v;
+    if (dstT) store_colmajor(dstT, hs, dw, x, y, v);
 }
 
 __global__ void undistort_kernel(Camera cam, const double* __restrict__ xy, int n, double* __restrict__ out) {
@@ -504,10 +528,15 @@ void launch_lm_reset(const LMReset& r, hipStream_t s) {
     lm_reset_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(r, maxP);
 }
 
-void launch_pyrdown(const uint8_t* src, int w, int h, uint8_t* dst, hipStream_t s) {
+void launch_pyrdown(const uint8_t* src, int w, int h, uint8_t* dst, hipStream_t s, uint8_t* dstT, int hs) {
     const int dw = (w + 1) / 2, dh = (h + 1) / 2;
     dim3 blk(32, 8), grd((dw + 31) / 32, (dh + 7) / 8);
-    pyrdown_kernel<<<grd, blk, 0, s>>>(src, w, h, dst);
+    pyrdown_kernel<<<grd, blk, 0, s>>>(src, w, h, dst, dstT, hs);
+}
+
+void launch_level_transpose(const uint8_t* src, int w, int h, uint8_t* dstT, int hs, hipStream_t s) {
+    dim3 blk(32, 32), grd((w + 31) / 32, (h + 31) / 32);
+    level_transpose_kernel<<<grd, blk, 0, s>>>(src, w, h, dstT, hs);
 }
 
 void launch_plane_project(const PlaneProjParams& p, hipStream_t s) {

@@ -764,8 +764,8 @@ int fm3d_internal_memory_need(fm3d_ctx* c, int64_t nA, int64_t nB, int dim, int 
     if ((r = ensure_offsets(c))) return r;
     const bool tree = c->s.lmReduction != 0;
     const int slots = fm3d::kLM2Slots + (tree ? 1 : 0);
-    const void* kptr = tree ? reinterpret_cast<const void*>(fm3d::lm2_kernel<true, true>)
-                            : reinterpret_cast<const void*>(fm3d::lm2_kernel<true, false>);
+    const void* kptr = tree ? reinterpret_cast<const void*>(fm3d::lm2_kernel<true, true, false>)
+                            : reinterpret_cast<const void*>(fm3d::lm2_kernel<true, false, false>);
     long groups = 0;
     if ((r = lm_groups(c, kptr, slots, -1, &groups))) return r;
     const size_t ents = (size_t)c->nOffPad * slots;
@@ -779,6 +779,8 @@ int fm3d_internal_memory_need(fm3d_ctx* c, int64_t nA, int64_t nB, int dim, int 
     if (c->s.crossCheck != 0) need += (size_t)(nA + nB) * (rowWork + 8) + (size_t)nB * (24 + 16 * 16);
     need += (size_t)nA * 1536;  // per query: top-2 lists + 16 parts, matches, points, masks, LM arrays, records
     need += (size_t)width * height * 4 + ((size_t)16 << 20);  // pyramids with guards, small buffers
+    // image 2's column-major levels: level 0's (w + 2) columns of stride <= h + 65, the others a third more
+    need += (size_t)(width + 2) * (height + 65) * 2;
     *bytes = need;
     return FM3D_OK;
 }
