@@ -158,8 +158,8 @@ __global__ void unpack_bits_kernel(const uint32_t* __restrict__ A, int nA, const
     if (train && w == 0) ctp[rr] = (int)pack_row((uint32_t)pc, rr);
 }
 
-// KS: dimPad / 32 when it is 4 (128-byte rows) or 8 (256), so the MFMA chain is straight-line
-// code; 0 reads it from dimPad.  BITS: rows are pre-unpacked int8 bits (no -128 offset, key
+// KS: dimPad / 32, 4 (128-byte rows) or 8 (256) -- the only row widths stage_descriptors and the bit
+// unpack produce -- so the MFMA chain is straight-line code.  BITS: rows are pre-unpacked int8 bits (no -128 offset, key
 // popc(b) - a.b', no query constant).  QG: 32-query groups per wave (a workgroup holds kQ * QG
 // queries); each A fragment read from LDS feeds QG MFMAs, and the per-tile staging, barrier and
 // merge are shared by QG groups.
@@ -186,11 +186,12 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
                                                            int tilesPerPart, int* __restrict__ idxOut,
                                                            int* __restrict__ keyOut, GateArgs<GATE> gate) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(KS == 4 || KS == 8, "rows of 128 or 256 bytes");
     static_assert(TR == 128 || (TR == 256 && KS == 4 && !BITS), "256-row tiles: 128-byte u8 rows only");
     constexpr int kRB = TR == 256 ? 8 : 7;                 // row bits of a packed key
     constexpr uint32_t kRowMask = (1u << kRB) - 1;
     constexpr uint32_t kBias = TR == 256 ? kKeyBias8 : kKeyBias;
-    const int tileBytes = TR * (KS ? 32 * KS : dimPad);
+    constexpr int tileBytes = TR * 32 * KS;
     unsigned char* tiles = smem;                              // 2 x tileBytes
     uint32_t* ctl = (uint32_t*)(smem + 2 * (size_t)tileBytes);  // 2 x TR packed row constants
     float2* uvl = (float2*)(ctl + 2 * TR);                      // kGateLane: 2 x TR train (u, v)
@@ -198,9 +199,9 @@ __global__ __launch_bounds__(kThreads) void knn2_i8_kernel(const uint8_t* __rest
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q0 = blockIdx.x * (kQ * QG) + wave * 32 * QG;
     const int half = lane >> 5;
-    const int ksteps = KS ? KS : dimPad / 32;
-    const int rowBytes = KS ? 32 * KS : dimPad;  // = dimPad (compile-time for KS != 0)
-    const int chunksPerRow = rowBytes / 16;
+    constexpr int ksteps = KS;
+    constexpr int rowBytes = 32 * KS;  // = dimPad
+    constexpr int chunksPerRow = rowBytes / 16;
     constexpr int kFlip = BITS ? 0 : (int)0x80808080;  // x ^ 0x80 == x - 128
     constexpr int kShift = BITS ? kRB : kRB + 1;         // acc * MUL << kRB (key bits start at bit kRB)
 
@@ -477,7 +478,7 @@ __device__ inline void top2_insert_f(float s, int j, float& b1, int& i1, float& 
 }
 
 // B in row pairs, interleaved element by element: P[(pr*DIM + d)*2 + k] = B[2pr + k][d] (zero
-// past nB, nPairs rounded up to even so that the kernel may read pair pr + 1 unconditionally)
+// past nB; knn2_f32_pairs_bytes counts the pairs so that the kernel may read pair pr + 1 unconditionally)
 __global__ void f32_row_pairs_kernel(const float* __restrict__ B, int nB, int dim, int nPairs, float* __restrict__ P) {
     const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (size_t)nPairs * dim * 2) return;
@@ -1401,7 +1402,7 @@ void launch_unpack_bits(const uint8_t* A, int nA, const uint8_t* B, int nB, uint
 void launch_knn2_i8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimPad, int bits, const int* cqA,
                     const int* ctB, int parts, int* partIdx, int* partKey, int* idx, int* key, hipStream_t s,
                     bool deferMerge, const EpiGate* gate) {
-    if (nA <= 0) return;
+    if (nA <= 0) return;  // (dimPad: 128 or 256, knn2_search refuses anything else)
     const int TRv = knn2_i8_tile_rows(dimPad, bits);
     const bool tile = gate && gate->transposed;  // lines on the tile (float4) instead of (u, v) (float2)
     size_t lds = 2 * (size_t)TRv * dimPad + 2 * TRv * sizeof(int) +
@@ -1435,10 +1436,8 @@ void launch_knn2_i8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimP
             goTile(knn2_i8_kernel<8, true, 1, kT, kGateTile>, 1);
         else if (dimPad == 128)
             goTile(knn2_i8_kernel<4, false, kQG128, kTR128, kGateTile>, kQG128);
-        else if (dimPad == 256)
-            goTile(knn2_i8_kernel<8, false, 1, kT, kGateTile>, 1);
         else
-            goTile(knn2_i8_kernel<0, false, 1, kT, kGateTile>, 1);
+            goTile(knn2_i8_kernel<8, false, 1, kT, kGateTile>, 1);
     } else if (gate) {
         // the same tile rows and queries per block as the ungated forms (knn2_i8_tile_rows,
         // knn2_i8_queries_per_block: the row constants' packing and the part count depend on them)
@@ -1446,18 +1445,14 @@ void launch_knn2_i8(const uint8_t* A, int nA, const uint8_t* B, int nB, int dimP
             goGated(knn2_i8_kernel<8, true, 1, kT, kGateLane>, 1);
         else if (dimPad == 128)
             goGated(knn2_i8_kernel<4, false, kQG128, kTR128, kGateLane>, kQG128);
-        else if (dimPad == 256)
-            goGated(knn2_i8_kernel<8, false, 1, kT, kGateLane>, 1);
         else
-            goGated(knn2_i8_kernel<0, false, 1, kT, kGateLane>, 1);
+            goGated(knn2_i8_kernel<8, false, 1, kT, kGateLane>, 1);
     } else if (bits)
         go(knn2_i8_kernel<8, true, 1>, 1);  // 32-byte binary rows unpacked to 256 int8
     else if (dimPad == 128)
         go(knn2_i8_kernel<4, false, kQG128, kTR128>, kQG128);
-    else if (dimPad == 256)
-        go(knn2_i8_kernel<8, false, 1>, 1);
     else
-        go(knn2_i8_kernel<0, false, 1>, 1);
+        go(knn2_i8_kernel<8, false, 1>, 1);
     if (parts > 1 && !deferMerge) knn2_int_merge<<<(nA + 255) / 256, 256, 0, s>>>(partIdx, partKey, nA, parts, idx, key);
 }
 
@@ -1619,7 +1614,10 @@ int knn2_parts(int nA, int nB, int dim, int nCU) {
 }
 
 size_t knn2_f32_pairs_bytes(int nB, int dim) {
-    size_t nPairs = ((size_t)(nB + 1) / 2 + 1) & ~(size_t)1;
+    // a part starts on an even row that need not be a multiple of four (launch_knn2_f32's rowsPerPart),
+    // so its last iteration may start at the last pair, (nB - 1) / 2, and read the one after it: one
+    // zero pair past the rows' own (nB + 1) / 2, whatever their parity
+    size_t nPairs = ((size_t)(nB + 1) / 2 + 2) & ~(size_t)1;
     if (nPairs < 2) nPairs = 2;  // nB = 0: still a (zero) launch grid
     return nPairs * dim * 2 * sizeof(float);
 }

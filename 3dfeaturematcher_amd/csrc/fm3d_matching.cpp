@@ -151,6 +151,8 @@ int knn2_search(fm3d_ctx* c, const DevBuf& A, const DevBuf& B, KnnWork& b, int n
         c->nCU = n > 0 ? n : 1;
     }
     if (type == FM3D_DESC_U8) {
+        // (stage_descriptors pads to one of the two; the kernel has no other form)
+        if (dimPad != 128 && dimPad != 256) return fail(c, FM3D_ERR_UNSUPPORTED, "u8 rows are matched at 128 or 256 bytes");
         const int nAPad = nA, nBPad = nB;
         HIPCHK(c, b.cq.ensure((size_t)(nAPad + 1) * sizeof(int)));
         HIPCHK(c, b.ct.ensure((size_t)(nBPad + 1) * sizeof(int)));

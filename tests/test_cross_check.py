@@ -120,6 +120,10 @@ KINDS = {  # name -> (oracle type, dim, binary)
     "u8-128": (1, 128, False), "u8-64": (1, 64, False), "u8-100": (1, 100, False), "u8-256": (1, 256, False),
     "f32-128": (0, 128, False), "f32-64": (0, 64, False), "f32-36": (0, 36, False),
     "bits-32": (2, 32, True), "bits-64": (2, 64, True),
+    # widths off the extractors' own: a 16-byte popcount scan, zero-padded binary rows, float rows with a
+    # tail after FLANN's groups of four, byte rows padded to 256 (tests/test_gpu_match_widths.py)
+    "bits-16": (2, 16, True), "bits-17": (2, 17, True), "bits-63": (2, 63, True),
+    "f32-5": (0, 5, False), "f32-65": (0, 65, False), "u8-129": (1, 129, False), "u8-255": (1, 255, False),
 }
 SHAPES = [(1, 1), (1, 2), (2, 1), (33, 129), (129, 33), (300, 700), (700, 300), (300, 5000), (5000, 300)]
 GUIDED_KINDS = ["u8-128", "u8-256", "f32-64", "f32-36", "bits-32", "bits-64"]

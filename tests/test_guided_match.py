@@ -101,8 +101,17 @@ KINDS = {  # name -> (oracle type, dim, binary)
     "u8-128": (1, 128, False), "u8-64": (1, 64, False), "u8-100": (1, 100, False), "u8-256": (1, 256, False),
     "f32-128": (0, 128, False), "f32-64": (0, 64, False), "f32-36": (0, 36, False),
     "bits-32": (2, 32, True), "bits-64": (2, 64, True),
+    # widths off the extractors' own: a 16-byte popcount scan, zero-padded binary rows, float rows with a
+    # tail after FLANN's groups of four, byte rows padded to 256 (tests/test_gpu_match_widths.py)
+    "bits-16": (2, 16, True), "bits-17": (2, 17, True), "bits-63": (2, 63, True),
+    "f32-5": (0, 5, False), "f32-65": (0, 65, False), "u8-129": (1, 129, False), "u8-255": (1, 255, False),
 }
+NEW_KINDS = ["bits-16", "bits-17", "bits-63", "f32-5", "f32-65", "u8-129", "u8-255"]
 SHAPES = [(1, 2), (33, 129), (300, 700), (2000, 5000)]
+# the new widths: the shapes up to (300, 700), and (300, 5000), where every gated kernel splits the train
+# rows into parts (the reference of (2000, 5000) is a per-query oracle call, seconds per kind)
+NEW_KIND_SHAPES = [(1, 2), (33, 129), (300, 700), (300, 5000)]
+KIND_SHAPES = [(k, s) for k in KINDS for s in (NEW_KIND_SHAPES if k in NEW_KINDS else SHAPES)]
 WIDTH, HEIGHT = 640, 480
 
 
@@ -193,8 +202,7 @@ def test_identity_pose_passes_nothing(fm3d, synth):
 
 
 # ---------------------------------------------------------------- 2. types and shapes
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
-@pytest.mark.parametrize("kind", list(KINDS))
+@pytest.mark.parametrize("kind,shape", KIND_SHAPES, ids=[f"{k}-{s[0]}x{s[1]}" for k, s in KIND_SHAPES])
 def test_types_and_shapes(fm3d, orc, ctx, kind, shape):
     nA, nB = shape
     typ, _, binary = KINDS[kind]
